@@ -15,8 +15,13 @@ gather + GEMMs) -> coarse-to-fine occupancy head (even-lattice upsample, occ_pro
 AdamW.  Workload = BASELINE.json configs[2] ("vocc.py coarse-to-fine multi-scale volume, bf16
 fwd+bwd"), i.e. the config the metric "viewpoints/sec (multi-view->voxel fwd+bwd), vocc.py
 config" is quoted on.  Inputs are resident in HBM before the timed region.  One JSON line on
-rank 0 (contract in the task statement), with `roofline` (fused gather kernel, HIP-event timed
-in the timed region) and `cpu_baseline` (the CPU oracle on this host's cores, N=1 only).
+rank 0 (contract in the task statement).
+
+A plain run sets up, runs the priming and warm-up steps, times `--steps` steps and prints the line.  `--full` adds
+everything else the line can carry: `roofline` / `roofline_other_kernels` (fused gather kernel and head GEMMs, HIP-event
+timed in the timed region), `config.latency`, `config.host_fed`, the `config.full_train` / `config.fp32` sub-records and
+`cpu_baseline` (the CPU oracle on this host's cores with its parity probe, N=1 only).  `--dump-outputs DIR` writes what
+the last timed step computed to DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import importlib
@@ -87,7 +92,17 @@ def parse():
     ap.add_argument('--sub-steps', type=int, default=3)
     ap.add_argument('--torch-optimizer', action='store_true',
                     help='clip_grad_norm_ + torch.optim.AdamW(fused=True) instead of optim.ClipAdamW (ver_clip_adamw_step)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='measure more than the headline: roofline / per-kernel figures (HIP events in the timed region), '
+                         'config.latency, config.host_fed, the --sub-records and the cpu_baseline leg with its parity probe; '
+                         'the options above that configure these only act with --full')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, '
+                         'seeded samples of large tensors, at most 64 MB in all)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def spawn_ranks(args):
@@ -159,15 +174,17 @@ def make_optimizer(params, own=True):
         opt = importlib.import_module('vln-ver_amd.optim').ClipAdamW(params, lr=1e-4, weight_decay=0.01, max_norm=300.0)
 
         def update():
-            opt.step()
+            norm = opt.step()
             opt.zero_grad(set_to_none=True)
+            return norm                                         # gradient norm before clipping (device scalar)
     else:
         opt = torch.optim.AdamW(params, lr=1e-4, weight_decay=0.01, fused=True)
 
         def update():
-            torch.nn.utils.clip_grad_norm_(params, 300.0)       # vocc.py:274 grad_clip max_norm
+            norm = torch.nn.utils.clip_grad_norm_(params, 300.0)    # vocc.py:274 grad_clip max_norm
             opt.step()
             opt.zero_grad(set_to_none=True)
+            return norm
     return opt, update
 
 
@@ -422,6 +439,126 @@ def sub_record(base, name, dev, rank, world, distributed):
     return rec
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_ELEMENTS = 8 << 20                  # float32 elements over all sampled tensors (32 MB)
+
+
+def dump_outputs(out_dir, last, outputs, model):
+    """--dump-outputs: what the last timed step computed, as a caller of the step receives it, written to
+    ``out_dir/<name>.npy``.  A training step: ``loss`` (float64 [1]), ``grad_norm`` (the gradient norm before clipping,
+    float64 [1]) and ``param.<name>`` for every parameter the step trains, after its update (float32).  The forward-only
+    workload: ``occupancy_mean`` (the step's return value, float64 [1]) and ``occupancy.<i>`` for every head micro-batch
+    of logits (float32).  A tensor larger than its share of DUMP_SAMPLE_ELEMENTS is written as a fixed sample: the
+    elements at sorted positions drawn without replacement by numpy's generator seeded with the crc32 of the name, so
+    two runs (or two builds) with the same arguments write the same positions."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if model is not None:
+        arrays['loss'] = last
+        arrays['grad_norm'] = outputs['grad_norm']
+        for k, p in model.named_parameters():
+            if p.requires_grad:
+                arrays['param.' + k] = p
+    else:
+        arrays['occupancy_mean'] = last
+        for i, t in enumerate(outputs['occupancy']):
+            arrays['occupancy.%d' % i] = t
+    big = [k for k, t in arrays.items() if t.numel() > 1]
+    share = max(1024, DUMP_SAMPLE_ELEMENTS // max(1, len(big)))
+    total = 0
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() == 1:
+            a = flat.double().cpu().numpy()
+        else:
+            if flat.numel() > share:
+                idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.numel(), share, replace=False))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            a = flat.float().cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, 'bench.py --dump-outputs: more than %d bytes' % DUMP_MAX_BYTES
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def roofline_figures(args, hip, timer, head, w2p, org, B, train, full, elapsed):
+    """(--full) -> (roofline, roofline_other_kernels) of the line: the fused gather kernels against the HBM peak and
+    the head's GEMMs against the MFMA peak, from the HIP events `timer` recorded around the launches of the timed steps."""
+    kt = timer.summary()
+    hit = hip.project_points(w2p, org, head.point_cloud_range, head.bev_z, head.bev_h, head.bev_w)
+    sigma_n = int(hit.vis_cnt.sum())
+    vbytes = 2 if args.dtype == 'bf16' else 4          # value_proj emits bf16 under autocast
+    fwd_b, bwd_b = gather_algorithmic_bytes(sigma_n, B, vbytes, grad_slots_bytes=2 if args.dtype == 'bf16' else 4)
+    roof, others = None, []
+    for name, byts, kernels in (('ver_sca_forward', fwd_b, ('k_sca_fwd', 'k_zero_rows')),
+                                ('ver_sca_backward', bwd_b, ('k_sca_bwd',))):
+        if name in kt and kt[name]['count']:
+            avg_ms = kt[name]['ms'] / kt[name]['count']
+            ach = byts / (avg_ms * 1e-3) / 1e9
+            traffic, src = measured_traffic(kernels, B)
+            obj = dict(kernel=name, bound='hbm', achieved=round(ach, 1), peak=HBM_PEAK_GBS, unit='GB/s',
+                       frac=round(ach / HBM_PEAK_GBS, 4), traffic=int(traffic) if traffic else None,
+                       traffic_source=(None if src is None else '%s (committed PMC pass of this command on another box, '
+                                       'keyed to the sha256 of csrc/ver_sca.hip; not a measurement of this run)' % src),
+                       avg_launch_us=round(avg_ms * 1e3, 2),
+                       launches=kt[name]['count'], algorithmic_bytes_per_launch=int(byts),
+                       value_bytes_per_element=vbytes, viewpoints_per_launch=B, sigma_n=sigma_n)
+            if name == 'ver_sca_forward':
+                # the zero fill of the rows the gather accumulates into (the reference's zeros_like inside the op,
+                # spatial_cross_attention.py:139) runs on a side stream under the projection GEMMs: its duration there,
+                # and what of it the launch stream still had to wait for in front of the gather (events on that stream
+                # around the join) -- `frac_with_zero_fill` prices the unhidden part with the kernel
+                zr, zw = kt.get('ver_sca_zero_rows'), kt.get('ver_sca_zero_wait')
+                if zr and zw and zr['count'] and zw['count']:
+                    fl = kt.get('ver_event_floor')
+                    floor_ms = fl['ms'] / fl['count'] if fl and fl['count'] else 0.0
+                    join_ms = zw['ms'] / zw['count']
+                    unhidden_ms = max(0.0, join_ms - floor_ms)
+                    obj['zero_fill'] = dict(side_stream_us=round(zr['ms'] / zr['count'] * 1e3, 2), join_us=round(join_ms * 1e3, 2),
+                                            empty_bracket_us=round(floor_ms * 1e3, 2), unhidden_us=round(unhidden_ms * 1e3, 2),
+                                            launches=zr['count'], bytes=int(hit.zero_cnt.sum()) * 768 * 4,
+                                            note='zero fill of the rows the gather accumulates into, on a side stream under the '
+                                                 'projection GEMMs; join = events on the launch stream around the wait for it, '
+                                                 'unhidden = join - an empty event bracket')
+                    obj['frac_with_zero_fill'] = round(byts / ((avg_ms + unhidden_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                roof = obj
+            else:
+                others.append(obj)
+    # the dense part (SURVEY 8d: "MFMA utilisation for the dense part"): the head's GEMMs -- the three lattice layers
+    # and occ_proj (which kernel runs which product: the `implementation` strings below) -- bracketed by HIP events on
+    # the launch stream in the timed region; flops = 2 m k n of every GEMM AS EXECUTED (with the constant / pad columns
+    # the operands carry, ~3 % over the useful count).  `whole_step` prices the USEFUL multiply-adds of one step
+    # (DESIGN section 3.4: 473.9 GFLOP per viewpoint forward, x 3 with the two backward products) on the step time.
+    classes = (('ver_gemm_nn', 'forward of the lattice layers: ver_gemm_nn_segments, operands read from the lattice (csrc/ver_gemm.hip)'),
+               ('head_gemm_fwd', 'forward of occ_proj (and of small batches): hipBLASLt N x N'),
+               ('head_gemm_dgrad', 'd(input): lattice layers ver_gemm_nn_planes (one product per layer, operands read from the '
+                                   'gradient lattice), occ_proj ver_gemm_nn (832-column groups) / hipBLASLt (768-column groups)'),
+               ('ver_wgrad_tn', 'd(weight): ver_wgrad_tn / ver_wgrad_tn_segments (csrc/ver_wgrad.hip)'))
+    tot_f = tot_ms = 0.0
+    for name, impl in classes:
+        if name in kt and kt[name]['ms'] > 0:
+            tf = kt[name]['flops'] / (kt[name]['ms'] * 1e-3) / 1e12
+            tot_f += kt[name]['flops']
+            tot_ms += kt[name]['ms']
+            others.append(dict(kernel=name, implementation=impl, bound='mfma', achieved=round(tf, 1), peak=MFMA_BF16_PEAK_TF,
+                               unit='TFLOP/s', frac=round(tf / MFMA_BF16_PEAK_TF, 4), launches=kt[name]['count'],
+                               ms_per_step=round(kt[name]['ms'] / args.steps, 3),
+                               tflop_per_step=round(kt[name]['flops'] / args.steps / 1e12, 3)))
+    if tot_ms > 0 and args.dtype == 'bf16':
+        tf = tot_f / (tot_ms * 1e-3) / 1e12
+        others.append(dict(kernel='head_gemms', bound='mfma', achieved=round(tf, 1), peak=MFMA_BF16_PEAK_TF, unit='TFLOP/s',
+                           frac=round(tf / MFMA_BF16_PEAK_TF, 4), ms_per_step=round(tot_ms / args.steps, 3),
+                           tflop_per_step=round(tot_f / args.steps / 1e12, 3),
+                           note='lattice layers 1-3 + occ_proj: forward, d(input), d(weight); HIP events, flops as executed'))
+    if train and not full and args.dtype == 'bf16' and args.workload == 'vocc_c2f_train' and args.config is None:
+        useful = 3 * 473.9e9 * B * args.steps                       # fwd + dgrad + wgrad of every GEMM of the path
+        tf = useful / elapsed / 1e12
+        others.append(dict(kernel='whole_step', bound='mfma', achieved=round(tf, 1), peak=MFMA_BF16_PEAK_TF, unit='TFLOP/s',
+                           frac=round(tf / MFMA_BF16_PEAK_TF, 4),
+                           note='useful multiply-adds of the step (473.9 GFLOP per viewpoint forward x 3) / step time'))
+    return roof, others
+
+
 def main():
     args = parse()
     # dmabuf IPC: the mode this image's host driver supports (task environment notes: without it RCCL / cross-process
@@ -493,6 +630,8 @@ def main():
         gt_boxes = [torch.from_numpy(g[0][:, :7]).to(dev) for g in gts]
         gt_labels = [torch.from_numpy(g[1]).to(dev) for g in gts]
 
+    outputs = {}                                # what the last eager step left besides its return value (--dump-outputs)
+
     def make_step(nb, graph=False):
         """One step over the first `nb` viewpoints of the resident inputs.  `graph` (full multi-task step on one rank
         only): the head's forward and backward are replayed as two hipGraphs (vln-ver_amd/graphs.py), everything else
@@ -519,11 +658,12 @@ def main():
             if train:
                 loss = ddp(f, w, o, g, gb, gl) if full else ddp(f, w, o, g)
                 loss.backward()
-                update()                                            # vocc.py:268-274: grad_clip + AdamW
+                outputs['grad_norm'] = update()                     # vocc.py:268-274: grad_clip + AdamW
                 return loss
             with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.dtype == 'bf16'):
                 emb = head(f, None, only_bev=True, world2pixel=w, origin=o)
                 out = [head.occupancy_from_volume(emb[s:s + args.micro]) for s in range(0, nb, args.micro)]
+                outputs['occupancy'] = out
                 return out[-1].float().mean()
         return step
 
@@ -553,7 +693,7 @@ def main():
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
-    timer = hip.KernelTimer()
+    timer = hip.KernelTimer() if args.full else None    # (the roofline figures: HIP events around the launches)
     hip.KERNEL_TIMER = timer
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -570,12 +710,15 @@ def main():
     elapsed = float(tmax)
     assert torch.isfinite(last).all(), 'non-finite loss'
     peak_gib = round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, outputs, model if train else None)
     last = None                                 # (no loss of an eager step may be alive when graphs are captured: graphs.py)
+    outputs.clear()
 
     # config.latency: the same step at the reference's own batch points (samples_per_gpu = 1, and 8),
     # measured AFTER the headline region and never part of `value`; every rank runs them (the gradient sum is collective)
     latency = []
-    for nb in [int(x) for x in args.latency_batches.split(',') if x.strip()]:
+    for nb in ([int(x) for x in args.latency_batches.split(',') if x.strip()] if args.full else []):
         if not train or nb > B:
             continue
         # the full multi-task step is host bound at these sizes (~1 500 module calls + as many autograd nodes): on one
@@ -612,7 +755,7 @@ def main():
     # in HOST memory (detectors/voxelformer.py:285-289) -- with the host -> HBM copy on the step's stream inside the timed
     # region.  The PCIe-inclusive rate; measured after the headline region, never part of `value`.
     host_fed = None
-    if train and args.host_fed_steps > 0:
+    if args.full and train and args.host_fed_steps > 0:
         host = torch.empty(feats.shape, dtype=feats.dtype, pin_memory=True)
         host.copy_(feats)
 
@@ -639,84 +782,14 @@ def main():
 
     # config.full_train / config.fp32: BASELINE configs[4] and the fp32 form of the headline workload on the driver's record
     subs = {}
-    if train and not full and args.dtype == 'bf16':
+    if args.full and train and not full and args.dtype == 'bf16':
         for name in [x.strip() for x in args.sub_records.split(',') if x.strip()]:
             subs[name.partition(':')[0]] = sub_record(args, name, dev, rank, world, distributed)
 
     exit_code = 0
     if rank == 0:
-        kt = timer.summary()
-        hit = hip.project_points(w2p, org, head.point_cloud_range, head.bev_z, head.bev_h, head.bev_w)
-        sigma_n = int(hit.vis_cnt.sum())
-        vbytes = 2 if args.dtype == 'bf16' else 4          # value_proj emits bf16 under autocast
-        fwd_b, bwd_b = gather_algorithmic_bytes(sigma_n, B, vbytes, grad_slots_bytes=2 if args.dtype == 'bf16' else 4)
-        roof, others = None, []
-        for name, byts, kernels in (('ver_sca_forward', fwd_b, ('k_sca_fwd', 'k_zero_rows')),
-                                    ('ver_sca_backward', bwd_b, ('k_sca_bwd',))):
-            if name in kt and kt[name]['count']:
-                avg_ms = kt[name]['ms'] / kt[name]['count']
-                ach = byts / (avg_ms * 1e-3) / 1e9
-                traffic, src = measured_traffic(kernels, B)
-                obj = dict(kernel=name, bound='hbm', achieved=round(ach, 1), peak=HBM_PEAK_GBS, unit='GB/s',
-                           frac=round(ach / HBM_PEAK_GBS, 4), traffic=int(traffic) if traffic else None,
-                           traffic_source=(None if src is None else '%s (committed PMC pass of this command on another box, '
-                                           'keyed to the sha256 of csrc/ver_sca.hip; not a measurement of this run)' % src),
-                           avg_launch_us=round(avg_ms * 1e3, 2),
-                           launches=kt[name]['count'], algorithmic_bytes_per_launch=int(byts),
-                           value_bytes_per_element=vbytes, viewpoints_per_launch=B, sigma_n=sigma_n)
-                if name == 'ver_sca_forward':
-                    # the zero fill of the rows the gather accumulates into (the reference's zeros_like inside the op,
-                    # spatial_cross_attention.py:139) runs on a side stream under the projection GEMMs: its duration there,
-                    # and what of it the launch stream still had to wait for in front of the gather (events on that stream
-                    # around the join) -- `frac_with_zero_fill` prices the unhidden part with the kernel
-                    zr, zw = kt.get('ver_sca_zero_rows'), kt.get('ver_sca_zero_wait')
-                    if zr and zw and zr['count'] and zw['count']:
-                        fl = kt.get('ver_event_floor')
-                        floor_ms = fl['ms'] / fl['count'] if fl and fl['count'] else 0.0
-                        join_ms = zw['ms'] / zw['count']
-                        unhidden_ms = max(0.0, join_ms - floor_ms)
-                        obj['zero_fill'] = dict(side_stream_us=round(zr['ms'] / zr['count'] * 1e3, 2), join_us=round(join_ms * 1e3, 2),
-                                                empty_bracket_us=round(floor_ms * 1e3, 2), unhidden_us=round(unhidden_ms * 1e3, 2),
-                                                launches=zr['count'], bytes=int(hit.zero_cnt.sum()) * 768 * 4,
-                                                note='zero fill of the rows the gather accumulates into, on a side stream under the '
-                                                     'projection GEMMs; join = events on the launch stream around the wait for it, '
-                                                     'unhidden = join - an empty event bracket')
-                        obj['frac_with_zero_fill'] = round(byts / ((avg_ms + unhidden_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-                    roof = obj
-                else:
-                    others.append(obj)
-        # the dense part ("MFMA utilisation for the dense part"): the head's GEMMs -- the three lattice layers
-        # and occ_proj (which kernel runs which product: the `implementation` strings below) -- bracketed by HIP events on
-        # the launch stream in the timed region; flops = 2 m k n of every GEMM AS EXECUTED (with the constant / pad columns
-        # the operands carry, ~3 % over the useful count).  `whole_step` prices the USEFUL multiply-adds of one step
-        # (473.9 GFLOP per viewpoint forward, x 3 with the two backward products) on the step time.
-        classes = (('ver_gemm_nn', 'forward of the lattice layers: ver_gemm_nn_segments, operands read from the lattice (csrc/ver_gemm.hip)'),
-                   ('head_gemm_fwd', 'forward of occ_proj (and of small batches): hipBLASLt N x N'),
-                   ('head_gemm_dgrad', 'd(input): lattice layers ver_gemm_nn_planes (one product per layer, operands read from the '
-                                       'gradient lattice), occ_proj ver_gemm_nn (832-column groups) / hipBLASLt (768-column groups)'),
-                   ('ver_wgrad_tn', 'd(weight): ver_wgrad_tn / ver_wgrad_tn_segments (csrc/ver_wgrad.hip)'))
-        tot_f = tot_ms = 0.0
-        for name, impl in classes:
-            if name in kt and kt[name]['ms'] > 0:
-                tf = kt[name]['flops'] / (kt[name]['ms'] * 1e-3) / 1e12
-                tot_f += kt[name]['flops']
-                tot_ms += kt[name]['ms']
-                others.append(dict(kernel=name, implementation=impl, bound='mfma', achieved=round(tf, 1), peak=MFMA_BF16_PEAK_TF,
-                                   unit='TFLOP/s', frac=round(tf / MFMA_BF16_PEAK_TF, 4), launches=kt[name]['count'],
-                                   ms_per_step=round(kt[name]['ms'] / args.steps, 3),
-                                   tflop_per_step=round(kt[name]['flops'] / args.steps / 1e12, 3)))
-        if tot_ms > 0 and args.dtype == 'bf16':
-            tf = tot_f / (tot_ms * 1e-3) / 1e12
-            others.append(dict(kernel='head_gemms', bound='mfma', achieved=round(tf, 1), peak=MFMA_BF16_PEAK_TF, unit='TFLOP/s',
-                               frac=round(tf / MFMA_BF16_PEAK_TF, 4), ms_per_step=round(tot_ms / args.steps, 3),
-                               tflop_per_step=round(tot_f / args.steps / 1e12, 3),
-                               note='lattice layers 1-3 + occ_proj: forward, d(input), d(weight); HIP events, flops as executed'))
-        if train and not full and args.dtype == 'bf16' and args.workload == 'vocc_c2f_train' and args.config is None:
-            useful = 3 * 473.9e9 * B * args.steps                       # fwd + dgrad + wgrad of every GEMM of the path
-            tf = useful / elapsed / 1e12
-            others.append(dict(kernel='whole_step', bound='mfma', achieved=round(tf, 1), peak=MFMA_BF16_PEAK_TF, unit='TFLOP/s',
-                               frac=round(tf / MFMA_BF16_PEAK_TF, 4),
-                               note='useful multiply-adds of the step (473.9 GFLOP per viewpoint forward x 3) / step time'))
+        roof, others = (roofline_figures(args, hip, timer, head, w2p, org, B, train, full, elapsed) if args.full
+                        else (None, None))
         total_vp = B * world * args.steps
         line = {
             'metric': 'viewpoints/sec (multi-view->voxel fwd+bwd), vocc.py config' if train
@@ -747,11 +820,12 @@ def main():
                                       'occupancy logits stay in the GEMM row order and the targets are permuted to match; '
                                       'on the bf16 path occ_branches[0] is composed with occ_proj every step '
                                       '(DESIGN.md sections 1, 3.3, 6)') if train else 'forward only',
-                       'latency': latency, 'host_fed': host_fed,
+                       'full': args.full,                # (False: the records below are None, measured with --full only)
+                       'latency': latency if args.full else None, 'host_fed': host_fed,
                        'full_train': subs.get('full_train'), 'fp32': subs.get('fp32')},
             'roofline': roof, 'roofline_other_kernels': others,
         }
-        if world == 1 and not args.no_cpu_baseline and train and not full:
+        if args.full and world == 1 and not args.no_cpu_baseline and train and not full:
             line['cpu_baseline'] = cpu_baseline(head, syn, args.cpu_seconds, dev, args.dtype)
         else:
             line['cpu_baseline'] = None

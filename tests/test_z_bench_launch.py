@@ -16,7 +16,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, 'bench.py')
-SMALL = ['--batch', '2', '--micro', '2', '--steps', '2', '--warmup', '0', '--no-cpu-baseline',
+# (--full: the records besides the headline -- roofline, config.latency, config.host_fed, sub-records -- that these tests check)
+SMALL = ['--batch', '2', '--micro', '2', '--steps', '2', '--warmup', '0', '--full', '--no-cpu-baseline',
          '--latency-batches', '1', '--latency-steps', '2', '--sub-records', '']
 
 
@@ -113,6 +114,43 @@ def test_plain_one_gpu_run_of_the_full_workload_replays_small_batches_as_graphs(
     rec = line['config']['latency'][0]
     assert rec['viewpoints_per_gpu_per_step'] == 1 and rec['graphed'] is True and rec['ms_per_step'] > 0
     assert line['config']['host_fed']['viewpoints_per_s'] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """`python bench.py` without --full: the line carries the headline and none of the --full records, and
+    `--dump-outputs DIR` writes the last timed step's loss, gradient norm and trained parameters.  Two runs with the same
+    arguments start from the same inputs and weights: their dumps name the same arrays, of the same shapes, and agree to
+    the atomics' summation order."""
+    import numpy as np
+    argv = ['--batch', '2', '--micro', '2', '--steps', '3', '--warmup', '1']
+    dumps = []
+    for run in (0, 1):
+        out = tmp_path / ('dump%d' % run)
+        proc = run_bench(argv + ['--dump-outputs', str(out)])
+        assert proc.returncode == 0, proc.stderr[-4000:]
+        line = json_line(proc)
+        assert line['steps'] == 3 and line['warmup'] == 1 and line['ms_per_step'] > 0 and line['value'] > 0
+        assert line['unit'] == 'viewpoints/s' and line['higher_is_better'] is True and line['dtype'] == 'bf16'
+        assert line['roofline'] is None and line['roofline_other_kernels'] is None and line['cpu_baseline'] is None
+        cfg = line['config']
+        assert cfg['full'] is False
+        assert cfg['latency'] is None and cfg['host_fed'] is None and cfg['full_train'] is None and cfg['fp32'] is None
+        files = sorted(os.listdir(out))
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        dumps.append({f: np.load(out / f) for f in files})
+    a, b = dumps
+    assert set(a) == set(b) and {'loss.npy', 'grad_norm.npy'} <= set(a)
+    assert sum(1 for f in a if f.startswith('param.')) > 50
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and a[f].shape == b[f].shape, f
+        assert np.isfinite(a[f]).all(), f
+    for f in ('loss.npy', 'grad_norm.npy'):
+        assert abs(float(a[f][0]) - float(b[f][0])) <= 1e-3 * abs(float(a[f][0])), (f, a[f], b[f])
+    worst = max(float(np.abs(a[f] - b[f]).max()) for f in a if f.startswith('param.'))
+    # (6 AdamW steps of lr 1e-4 -- 2 priming, 1 warm-up, 3 timed: an element whose gradient is within rounding of zero may
+    #  take a different sign in the two runs; everything else agrees to rounding)
+    assert worst <= 2e-3, worst
 
 
 @pytest.mark.gpu
