@@ -497,8 +497,10 @@ int  ver_wgrad_tn(const void* a, long lda, const void* g, long ldg, long M, int 
 /*   the same product with the IMPLICIT tap matrix of ver_gemm_nn_segments as A (ABI 29): out[Ka, N] = A^T g, A's columns =
  *   the segments in order (taps int [nseg][3]: (dz, dy, dx) = C columns, (-1 - k, 0, 0) = the cw columns of pattern block k of
  *   cst), rows = the cells of the combined (H, W) lattice, M = B 2 H W.  Segment widths must be multiples of 64 (a wave's
- *   64-column LDS-DMA piece lies inside one segment): C % 64 == 0, cw % 64 == 0.  2 H W < 65 536, the source lattice below
- *   2 GiB.  ver_wgrad_tn_segments_splits: the row-chunk count for `splits` = 0 (sizes the workspace f32 [splits][Ka][N]). */
+ *   64-column LDS-DMA piece lies inside one segment): C % 64 == 0, cw % 64 == 0.  16 <= 2 H W <= 2 048 rows per viewpoint
+ *   (four per-wave offset tables of 2 H W ints sit next to the 128-KiB ring: 160 KiB, all of a CU's LDS, at 2 048), the source
+ *   lattice below 2 GiB (the forward, ver_gemm_nn_taps / _segments / _planes, has no bound on 2 H W).
+ *   ver_wgrad_tn_segments_splits: the row-chunk count for `splits` = 0 (sizes the workspace f32 [splits][Ka][N]). */
 int  ver_wgrad_tn_segments(const void* lattice, int layout, int B, int H, int W, int C, const int* taps, int nseg, const void* cst,
                            int ncst, int cw, const void* g, long ldg, int N, void* out, long ldo, int out_dtype, int splits,
                            void* workspace, long workspace_bytes, void* stream);

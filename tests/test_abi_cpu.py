@@ -189,6 +189,52 @@ def test_argument_validation_of_the_gemm_entry_points():
     assert rc == -1 and b'null' in lib.ver_last_error()
 
 
+class _LatticeStandIn:
+    """What the admission predicates read of a lattice (a contiguous bf16 GPU tensor of ``n`` elements), without a GPU."""
+    is_cuda, dtype = True, torch.bfloat16
+
+    def __init__(self, n):
+        self.n = n
+
+    def is_contiguous(self):
+        return True
+
+    def numel(self):
+        return self.n
+
+
+def test_wgrad_segments_rows_per_viewpoint_bound_is_the_python_admission_rule(monkeypatch):
+    """ver_wgrad_tn_segments takes 16 <= 2 H W <= 2 048 rows per viewpoint (four offset tables of 2 H W ints next to the
+    128-KiB ring fill a CU's 160 KiB of LDS).  At 2 H W = 2 048 (32 x 32) the launcher gets past that check and stops at the
+    next one, a g row pitch that is not a multiple of 8; at 2 050 (25 x 41) it stops at the rows check.  The Python side
+    (hipops.wgrad_tn_segments_supported, and upsample._implicit_taps, which sends a layer to the implicit kernels) draws the
+    line in the same place, so a layer never runs its forward implicitly and then finds its weight gradient refused."""
+    hip, ups = pkg('hipops'), pkg('dense_heads.upsample')
+    lib = hip.lib()
+    L = ctypes.c_long
+    C, N = 64, 64
+    taps = (ctypes.c_int * 3)(0, 0, 0)
+    buf = (ctypes.c_float * 64)()
+    seg = lambda h, w, ldg: (buf, 2, 1, h, w, C, taps, 1, None, 0, 0, buf, L(ldg), N, buf, L(N), 0, 1, buf, L(1 << 30), None)
+    rc = lib.ver_wgrad_tn_segments(*seg(32, 32, N + 1))
+    assert rc == -2 and b'row pitch' in lib.ver_last_error(), lib.ver_last_error()
+    rc = lib.ver_wgrad_tn_segments(*seg(25, 41, N + 1))
+    assert rc == -2 and b'2050 rows per viewpoint' in lib.ver_last_error(), lib.ver_last_error()
+    rc = lib.ver_wgrad_tn_segments(*seg(1, 7, N + 1))                        # the lower end: 14 rows < one 16-row slab
+    assert rc == -2 and b'14 rows per viewpoint' in lib.ver_last_error(), lib.ver_last_error()
+    assert hip.WGRAD_SEGMENTS_ROWS == (16, 2048)
+    lat = lambda h, w: _LatticeStandIn(4 * h * w * C)
+    for (h, w), ok in (((32, 32), True), ((16, 64), True), ((25, 41), False), ((40, 40), False), ((2, 4), True), ((1, 7), False)):
+        assert hip.wgrad_tn_segments_supported(lat(h, w), 2, (h, w), C, 192, None) == ok, (h, w)
+        assert hip.gemm_nn_taps_supported(lat(h, w), 2, None, C)             # (the forward takes every one of them)
+        # the layer's decision: implicit only where both kernels take the shape
+        monkeypatch.setattr(ups, '_OWN_GEMM_MIN_ROWS', 0)
+        monkeypatch.setattr(ups, '_IMPLICIT_TAPS', True)
+        monkeypatch.setattr(ups, '_OWN_GEMM', True)
+        assert ups._implicit_taps(lat(h, w), 2, 2 * h * w, (h, w), C, object(), ups._PW2) == ok, (h, w)
+        assert ups._implicit_taps(lat(h, w), 0, 2 * h * w, (h, w), C, object(), 0) == ok, (h, w)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason='checks the no-GPU failure mode')
 def test_ops_refuse_cpu_tensors():
     hip = pkg('hipops')

@@ -570,9 +570,8 @@ extern "C" int ver_wgrad_tn(const void* a, long lda, const void* g, long ldg, lo
             default: launch_tn<1, 3>(p, p.T * S, st, e); break;
         }
         if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_wgrad_tn: LDS attribute: %s", hipGetErrorString(e));
-    } else {
-        e = hipMemsetAsync(workspace, 0, (size_t)S * Ka * N * sizeof(float), st);
-        if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_wgrad_tn: memset: %s", hipGetErrorString(e));
+    } else if (int zrc = ver_zero_async(workspace, (size_t)S * Ka * N * sizeof(float), st)) {   // (kernel zero fill: ver_zero_async)
+        return zrc;
     }
     if (direct) return ver_check_launch("ver_wgrad_tn");
     const long n4 = (long)Ka * N / 4;
@@ -658,9 +657,8 @@ extern "C" int ver_wgrad_tn_segments(const void* lattice, int layout, int B, int
         else if (layout == 2) launch_tn_segments<2>(p, p.T * S, st, e);
         else launch_tn_segments<3>(p, p.T * S, st, e);
         if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_wgrad_tn_segments: LDS attribute: %s", hipGetErrorString(e));
-    } else {
-        e = hipMemsetAsync(workspace, 0, (size_t)S * Ka * N * sizeof(float), st);
-        if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_wgrad_tn_segments: memset: %s", hipGetErrorString(e));
+    } else if (int zrc = ver_zero_async(workspace, (size_t)S * Ka * N * sizeof(float), st)) {   // (kernel zero fill: ver_zero_async)
+        return zrc;
     }
     if (direct) return ver_check_launch("ver_wgrad_tn_segments");
     const long n4 = Ka * N / 4;

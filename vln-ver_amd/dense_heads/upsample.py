@@ -518,13 +518,16 @@ _IMPLICIT_DGRAD = os.environ.get('VER_IMPLICIT_TAPS', '1') == '1'
 _IMPLICIT_WGRAD = os.environ.get('VER_IMPLICIT_TAPS', '1') != '2'
 
 
-def _implicit_taps(e, layout, rows, hw, ci, raw):
-    """True when a layer with source lattice ``e`` (layout 0 / 2 / 3), ``rows`` = B * 2 * H * W and H * W = ``hw`` takes the
-    implicit-operand kernels."""
+def _implicit_taps(e, layout, rows, combined_hw, ci, raw, const_width):
+    """True when a layer with source lattice ``e`` (layout 0 / 2 / 3), ``rows`` = B * 2 * H * W over the combined (H, W) lattice
+    and pattern blocks of ``const_width`` columns (0: none) takes the implicit-operand kernels.  THE place that decides: the
+    forward product (ver_gemm_nn_segments) and the weight gradient (ver_wgrad_tn_segments) must both take the shape, or the
+    layer runs on explicit tap matrices in both passes -- ver_wgrad_tn_segments stops at 2 H W = 2 048 (its offset tables in
+    LDS), so e.g. layer 3 of a 20 x 20 BEV grid (2 H W = 3 200) goes the explicit way, as it did before the implicit kernels."""
     if not (_IMPLICIT_TAPS and _OWN_GEMM and raw is not None and _on_hip(e) and e.dtype == torch.bfloat16 and rows >= _OWN_GEMM_MIN_ROWS):
         return False
-    return (e.is_contiguous() and e.numel() * 2 < 2 ** 31 - 1 and ci % 64 == 0 and ci >= 64 and 16 <= 2 * hw < 65536
-            and _PW2 % 64 == 0)
+    from ..hipops import gemm_nn_taps_supported, wgrad_tn_segments_supported
+    return gemm_nn_taps_supported(e, layout, None, ci) and wgrad_tn_segments_supported(e, layout, combined_hw, ci, const_width, None)
 
 
 _DGRAD_PLAN = {}
@@ -588,7 +591,7 @@ class _Layer0Z4(torch.autograd.Function):
         ctx.raw = raw is not None
         co = raw.shape[1] if raw is not None else k.shape[-1]
         taps, offs, lo, hi = _layer0_z4_plan(ci, x.device)
-        ctx.implicit = _implicit_taps(x, ZS_PLAIN, b * 2 * h * w, h * w, ci, raw)
+        ctx.implicit = _implicit_taps(x, ZS_PLAIN, b * 2 * h * w, (h, w), ci, raw, 0)
         if ctx.implicit:
             from ..hipops import convt_weight_forward_blocks, gemm_nn_taps
             x = x.contiguous()
@@ -833,7 +836,7 @@ class _LatticeLayerZ4(torch.autograd.Function):
         dt = e.dtype
         plan, kt, total_rows, taps, offs = _layer_plan_z4(ci, e.device)
         m = b * 2 * hc * wc
-        ctx.implicit = _implicit_taps(e, layout, m, hc * wc, ci, raw)
+        ctx.implicit = _implicit_taps(e, layout, m, (hc, wc), ci, raw, _PW2)
         a_mat = None if ctx.implicit else e.new_empty(m, kt)
         if not ctx.implicit and not _gather_z4(e, layout, a_mat, taps, offs, ci, hc, wc, with_const=True):
             pats = _class_patterns(4, hc, wc, e.device, dt)

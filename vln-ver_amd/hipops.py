@@ -1290,10 +1290,11 @@ def gemm_nn(a, w, bias=None, out=None, splits=None, timer_class='ver_gemm_nn'):
 
 def gemm_nn_taps_supported(lattice, layout, w, c):
     """What ``gemm_nn_taps`` takes: a contiguous bf16 lattice below 2 GiB in layout 0 / 2 / 3 with C % 32 == 0, a bf16 weight
-    matrix with 16-byte aligned rows."""
+    matrix with 16-byte aligned rows (``w`` None: the lattice side only, before the weights exist).  Any 2 H W."""
     return (lattice.is_cuda and lattice.dtype == torch.bfloat16 and lattice.is_contiguous() and layout in (PLAIN, ZSPLIT, PLANAR_ZSPLIT)
-            and lattice.numel() * 2 < 2 ** 31 - 1 and c % 32 == 0 and c >= 64 and w.is_cuda and w.dtype == torch.bfloat16
-            and w.dim() == 2 and w.stride(1) == 1 and w.stride(0) % 8 == 0 and w.data_ptr() % 16 == 0)
+            and lattice.numel() * 2 < 2 ** 31 - 1 and c % 32 == 0 and c >= 64
+            and (w is None or (w.is_cuda and w.dtype == torch.bfloat16 and w.dim() == 2 and w.stride(1) == 1 and w.stride(0) % 8 == 0
+                               and w.data_ptr() % 16 == 0)))
 
 
 def gemm_nn_taps(lattice, layout, combined_hw, taps, w, rowpos=None, bias=None, out=None, const_rows=None, planes=None,
@@ -1366,12 +1367,21 @@ def _segment_args(lat, layout, combined_hw, taps, const_rows, name):
     return B, H, W, C, const_rows, ncst, cw, kdim, (ctypes.c_int * len(flat))(*flat), len(taps)
 
 
-def wgrad_tn_segments_supported(lattice, layout, c, const_width, g):
-    """What ``wgrad_tn_segments`` takes (segment widths multiples of 64, the lattice below 2 GiB, 2 H W < 65 536 checked by
-    the library)."""
-    return (lattice.is_cuda and lattice.dtype == torch.bfloat16 and lattice.is_contiguous() and layout in (PLAIN, ZSPLIT, PLANAR_ZSPLIT)
-            and lattice.numel() * 2 < 2 ** 31 - 1 and c % 64 == 0 and const_width % 64 == 0 and g.is_cuda and g.dtype == torch.bfloat16
-            and g.dim() == 2 and g.stride(1) == 1 and g.stride(0) % 8 == 0 and g.data_ptr() % 16 == 0 and g.shape[1] % 4 == 0)
+# rows per viewpoint (2 H W) ver_wgrad_tn_segments takes: its four per-wave offset tables of 2 H W ints sit next to the 128-KiB
+# operand ring in LDS, and 128 KiB + 4 x 4 x 2 048 B is all of a gfx950 CU's 160 KiB (csrc/ver_wgrad.hip)
+WGRAD_SEGMENTS_ROWS = (16, 2048)
+
+
+def wgrad_tn_segments_supported(lattice, layout, combined_hw, c, const_width, g):
+    """What ``wgrad_tn_segments`` takes -- the library's rules: 16 <= 2 H W <= 2 048 rows per viewpoint of the combined (H, W)
+    lattice, segment widths multiples of 64, the lattice below 2 GiB; ``g`` None: the lattice side only (a layer's forward
+    pass decides before its output gradient exists)."""
+    H, W = combined_hw
+    return (WGRAD_SEGMENTS_ROWS[0] <= 2 * H * W <= WGRAD_SEGMENTS_ROWS[1]
+            and lattice.is_cuda and lattice.dtype == torch.bfloat16 and lattice.is_contiguous() and layout in (PLAIN, ZSPLIT, PLANAR_ZSPLIT)
+            and lattice.numel() * 2 < 2 ** 31 - 1 and c % 64 == 0 and const_width % 64 == 0
+            and (g is None or (g.is_cuda and g.dtype == torch.bfloat16 and g.dim() == 2 and g.stride(1) == 1 and g.stride(0) % 8 == 0
+                               and g.data_ptr() % 16 == 0 and g.shape[1] % 4 == 0)))
 
 
 def wgrad_tn_segments(lattice, layout, combined_hw, taps, g, out_dtype=None, out=None, const_rows=None, splits=0):
@@ -1379,7 +1389,7 @@ def wgrad_tn_segments(lattice, layout, combined_hw, taps, g, out_dtype=None, out
     gradient of a lattice layer's class GEMM, [sum of the segment widths, N] in ``out_dtype`` (``out``: a matrix to write into)."""
     lat, g = _gpu(lattice, 'lattice'), _gpu(g, 'g')
     B, H, W, C, const_rows, ncst, cw, ka, arr, nseg = _segment_args(lat, layout, combined_hw, taps, const_rows, 'wgrad_tn_segments')
-    if not wgrad_tn_segments_supported(lat, int(layout), C, cw, g):
+    if not wgrad_tn_segments_supported(lat, int(layout), (H, W), C, cw, g):
         raise RuntimeError('wgrad_tn_segments: unsupported operands %s layout %d / %s %s' % (tuple(lat.shape), layout, tuple(g.shape), g.stride()))
     if g.shape[0] != B * 2 * H * W:
         raise ValueError('wgrad_tn_segments: g has %d rows, %d cells' % (g.shape[0], B * 2 * H * W))
