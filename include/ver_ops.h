@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define VER_ABI_VERSION 29
+#define VER_ABI_VERSION 30
 
 #define VER_OK            0
 #define VER_EINVAL       -1   /* bad argument (null pointer, non-positive size, ...) */
@@ -472,6 +472,24 @@ int ver_occ_mlp_backward_fused_stats(const void* x, const void* grad_logits, con
 long ver_occ_predict_blocks(long N);
 int  ver_occ_predict(const void* logits, int dtype, long N, int C, float threshold, int32_t* block_work,
                      int64_t* pairs, int64_t* count, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Occupancy IoU / mIoU confusion matrix (ABI 30): the numpy `bincount` of the reference's
+ * SSCMetrics.add_batch (datasets/occupancy_metrics.py) fed by MP3DDataset.evaluate_occ_iou
+ * (mp3docc_dataset.py:485-584), for T thresholds in one pass over the logits.
+ *   logits      f32|bf16 [samples * rows_per_sample, C]   (16-byte aligned, C % 8 == 0, 8 <= C <= 32)
+ *   labels      u8 [samples * rows_per_sample], same row order; a value >= C + 1 is ignored (the
+ *               reference's `gt < n_cl`: pass invalid / invisible voxels as 255)
+ *   thresholds  HOST f32 [num_thresholds], 1 <= num_thresholds <= 8 (copied into the kernel arguments:
+ *               a captured launch keeps them)
+ *   hist        i64 [samples, num_thresholds, K, K], K = C + 1; row = label, column = prediction,
+ *               column C = empty.  ACCUMULATED (+=): zero it once at allocation; nothing is cleared here.
+ * The prediction of a row under threshold t is the class ver_occ_predict gives with that threshold
+ * (fp32 sigmoid, first of equal maxima, NaN as the maximum, class C when thr_t > every probability).
+ * rows_per_sample == 0 or samples == 0: nothing is launched, hist is unchanged.
+ */
+int  ver_occ_confusion(const void* logits, int dtype, long rows_per_sample, int samples, int C, const uint8_t* labels,
+                       const float* thresholds, int num_thresholds, int64_t* hist, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Weight gradient of the head's GEMM layers with ROWS on the contraction axis (ABI 24):

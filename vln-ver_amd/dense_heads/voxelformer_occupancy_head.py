@@ -51,6 +51,30 @@ def _to_device_async(t, dev):
     return t.pin_memory().to(dev, non_blocking=True)
 
 
+def _confusion(logits, labels, samples, thresholds, hist):
+    """hist[s, t] += confusion matrix of sample s under threshold t (``VoxelFormerOccupancyHead.occupancy_confusion``):
+    logits [samples * rows, C], labels one per row in the same order.  ``ver_occ_confusion`` on the GPU; for CPU tensors
+    or a class count the kernel is not built for, the same counts as torch ops (the reference's prediction of
+    ``get_occupancy_prediction`` -- fp32 sigmoid, the threshold column, ``argmax`` -- and ``bincount`` over
+    ``gt * K + pred`` for ``gt < K``)."""
+    c = logits.shape[-1]
+    logits = logits.reshape(-1, c)
+    labels = labels.reshape(-1)
+    if logits.is_cuda and c % 8 == 0 and 8 <= c <= 32:
+        from ..hipops import occ_confusion
+        return occ_confusion(logits, labels.to(torch.uint8), thresholds, samples, hist)
+    k = c + 1
+    p = logits.float().sigmoid()
+    gt = labels.long().view(samples, -1)
+    keep = gt < k
+    first = torch.arange(samples, device=gt.device)[:, None] * k + gt           # (sample, label) row of the histogram
+    for t, thr in enumerate(thresholds):
+        pred = torch.cat((p, torch.full_like(p[:, :1], thr)), dim=-1).argmax(dim=-1).view(samples, -1)
+        counts = torch.bincount((first * k + pred)[keep], minlength=samples * k * k)
+        hist[:, t] += counts.view(samples, k, k).to(hist.device)
+    return hist
+
+
 def bias_init_with_prob(prior_prob):
     return float(-math.log((1 - prior_prob) / prior_prob))
 
@@ -691,6 +715,52 @@ class VoxelFormerOccupancyHead(BaseModule):
             if pairs.numel():
                 gt[b, pairs[:, 0]] = pairs[:, 1]
         return gt
+
+    def occupancy_eval_labels(self, occ_gts, occ_invalid=None, device=None):
+        """The evaluation labels of ``MP3DDataset.evaluate_occ_iou`` (mp3docc_dataset.py:500-514) as bytes: ``occ_gts`` as
+        in ``occupancy_targets``; ``occ_invalid[b]`` (or None) the voxel indices of the ``occ_invalid_path`` file, whose
+        voxels leave the visible mask.  -> uint8 [bs, voxel_num] in the reference's voxel order: ``occupancy_classes`` =
+        empty, 255 = not evaluated (``occupancy_confusion`` ignores every label above ``occupancy_classes``)."""
+        device = device if device is not None else self.code_weights.device
+        gt = torch.full((len(occ_gts), self.voxel_num), self.occupancy_classes, dtype=torch.uint8, device=device)
+        for b, pairs in enumerate(occ_gts):
+            if isinstance(pairs, (list, tuple)):                   # occ_gts[bs][queue_index]
+                pairs = pairs[0]
+            pairs = torch.as_tensor(pairs).long().to(device)
+            if pairs.numel():
+                gt[b, pairs[:, 0]] = pairs[:, 1].to(torch.uint8)
+            invalid = occ_invalid[b] if occ_invalid is not None else None
+            if invalid is not None:
+                invalid = torch.as_tensor(invalid).long().reshape(-1).to(device)
+                if invalid.numel():
+                    gt[b, invalid] = 255
+        return gt
+
+    def occupancy_confusion(self, occupancy_preds, labels, thresholds=(0.25,), hist=None):
+        """Confusion matrices of the occupancy prediction of ``get_occupancy_prediction`` at every threshold against
+        ``labels`` (``occupancy_eval_labels``), per sample: -> int64 [bs, T, K, K], K = classes + 1, row = label,
+        column = prediction (the histogram ``SSCMetrics.add_batch`` accumulates); ``hist`` of that shape: accumulated into.
+        ``occupancy_preds``: the reference-order logits [bs, N, classes] of ``forward``, or the row-order tuple of
+        ``occupancy_rows=True`` / ``occupancy_from_volume(..., rows_only=True)``, whose LABELS are brought into the
+        logits' row order (a histogram does not depend on the order of its pairs).  GPU logits with a class count the
+        kernel is built for: one ``ver_occ_confusion`` pass per row block; otherwise the same counts in torch."""
+        thresholds = tuple(float(t) for t in thresholds)
+        nc = self.occupancy_classes
+        if isinstance(occupancy_preds, tuple):                         # (logits in GEMM row order, plan, bs)
+            logits, plan, bs = occupancy_preds                         # [bs*X*Y, Z, classes], group-major rows
+            gt = labels.reshape(bs, self.occ_zdim, plan.rows).permute(0, 2, 1)      # (Z, X, Y) order -> [bs, X*Y, Z]
+            gt = voxels_to_rows(gt, plan, bs)
+            if hist is None:
+                hist = torch.zeros((bs, len(thresholds), nc + 1, nc + 1), dtype=torch.int64, device=logits.device)
+            # the rows of sample b in group g are contiguous (row bs*offset_g + b*n_g + i): one call per group
+            for g in plan.groups:
+                sl = slice(bs * g.offset, bs * (g.offset + g.n_rows))
+                _confusion(logits[sl], gt[sl], bs, thresholds, hist)
+            return hist
+        bs = occupancy_preds.shape[0] if occupancy_preds.dim() == 3 else 1
+        if hist is None:
+            hist = torch.zeros((bs, len(thresholds), nc + 1, nc + 1), dtype=torch.int64, device=occupancy_preds.device)
+        return _confusion(occupancy_preds, labels, bs, thresholds, hist)
 
     def loss_only_occupancy(self, gt_bboxes_list, gt_labels_list, gt_occupancy, preds_dicts):
         """``only_occ`` detectors (head:1387-1447): the occupancy focal loss alone, plus the zero ``loss_flow``."""

@@ -197,6 +197,29 @@ class VoxelFormer(BaseModule):
                 result_dict['pts_bbox'] = pts_bbox
         return new_prev_bev, bbox_list, occ_results
 
+    def evaluate_occupancy(self, img_metas, metrics=None, thresholds=(0.25,), autocast_dtype=None):
+        """The occupancy evaluation of ``simple_test`` followed by ``MP3DDataset.evaluate_occ_iou``
+        (mp3docc_dataset.py:485-584) for a batch of viewpoints, on the device: the lifting path alone (no decoder, logits
+        left in the GEMMs' row order), labels from each meta's ``occ_gt_path`` (sparse (index, class) pairs) and optional
+        ``occ_invalid_path`` (voxel indices outside the visible mask), the confusion matrices of every threshold
+        counted into ``metrics`` (an ``occupancy_metrics.DeviceSSCMetrics``; a new one with ``thresholds`` when None;
+        its own thresholds otherwise).  ``autocast_dtype``: 'bf16' runs the path under bf16 autocast.  -> ``metrics``."""
+        from ..occupancy_metrics import DeviceSSCMetrics
+        head = self.pts_bbox_head
+        dev = self._device()
+        if metrics is None:
+            metrics = DeviceSSCMetrics(head.occupancy_classes + 1, thresholds, device=dev)
+        lowp = {'bf16': torch.bfloat16, 'fp16': torch.float16}.get(autocast_dtype, autocast_dtype)
+        img_feats = self.viewpoint_features(img_metas)
+        occ_gts = [np.load(m['occ_gt_path']) for m in img_metas]
+        invalid = [np.load(m['occ_invalid_path']) if m.get('occ_invalid_path') else None for m in img_metas]
+        labels = head.occupancy_eval_labels(occ_gts, invalid, device=dev)
+        with torch.no_grad(), torch.autocast('cuda', dtype=lowp or torch.bfloat16, enabled=lowp is not None and img_feats.is_cuda):
+            voxel_embed = head(img_feats, img_metas, only_bev=True)
+            preds = head.occupancy_from_volume(voxel_embed, rows_only=True)
+        metrics.add(head, preds, labels)
+        return metrics
+
     def simple_test_pts(self, x, img_metas, prev_bev=None, rescale=False):
         """:376-391."""
         outs = self.pts_bbox_head(x, img_metas, prev_bev=prev_bev)

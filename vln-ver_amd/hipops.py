@@ -14,7 +14,7 @@ from torch.autograd.function import once_differentiable
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # (VER_HIP_LIB: another build of the same ABI, e.g. the host-ASan build libver_hip_asan.so of tests/test_abi_cpu.py)
 LIB_PATH = os.environ.get('VER_HIP_LIB') or os.path.join(_PKG, 'libver_hip.so')
-ABI_VERSION = 29
+ABI_VERSION = 30
 SYMBOLS = ('ver_abi_version', 'ver_last_error', 'ver_sca_backward_grad_dtype', 'ver_msda_forward', 'ver_msda_backward',
            'ver_project_points', 'ver_hits_from_mask', 'ver_sca_zero_rows', 'ver_sca_head_major_supported',
            'ver_sca_forward', 'ver_sca_backward',
@@ -24,7 +24,7 @@ SYMBOLS = ('ver_abi_version', 'ver_last_error', 'ver_sca_backward_grad_dtype', '
            'ver_occ_mlp_forward', 'ver_occ_mlp_backward', 'ver_occ_mlp_backward_fused', 'ver_lattice_gather', 'ver_lattice_scatter',
            'ver_convt_weight_forward', 'ver_convt_weight_backward', 'ver_convt_weight_backward_blocks', 'ver_convt_weight_forward_blocks', 'ver_blocks_vec_forward', 'ver_blocks_vec_backward', 'ver_lattice_transpose', 'ver_lattice_rows', 'ver_run_gather',
            'ver_run_scatter', 'ver_add_ln_forward', 'ver_add_ln_backward',
-           'ver_relu_dropout_forward', 'ver_relu_dropout_backward', 'ver_occ_predict_blocks', 'ver_occ_predict',
+           'ver_relu_dropout_forward', 'ver_relu_dropout_backward', 'ver_occ_predict_blocks', 'ver_occ_predict', 'ver_occ_confusion',
            'ver_wgrad_tn_splits', 'ver_wgrad_tn_splits_ld', 'ver_wgrad_tn_segments', 'ver_wgrad_tn_segments_splits', 'ver_wgrad_tn_workspace', 'ver_wgrad_tn', 'ver_occ_mlp_forward_stats',
            'ver_occ_mlp_backward_fused_stats', 'ver_gemm_nn', 'ver_gemm_nn_splits', 'ver_gemm_nn_splitk', 'ver_gemm_nn_taps', 'ver_gemm_nn_segments', 'ver_gemm_nn_planes', 'ver_clip_adamw_step', 'ver_clip_adamw_step_tensors')
 
@@ -1210,6 +1210,38 @@ def occ_predict(logits, threshold=0.25):
     _launch('ver_occ_predict', lambda: lib().ver_occ_predict(
         _p(logits), dt, ctypes.c_long(n), c, ctypes.c_float(threshold), _p(work), _p(pairs), _p(count), _stream()))
     return pairs[:int(count.item())]
+
+
+def occ_confusion(logits, labels, thresholds=(0.25,), samples=1, hist=None):
+    """Occupancy confusion matrix (ver_occ_confusion; the histogram of the reference's ``SSCMetrics.add_batch``):
+    logits fp32|bf16 [samples * rows, C] (any leading shape), labels u8 with one entry per logit row in the same order
+    (``>= C + 1``: ignored) -> int64 hist [samples, T, C + 1, C + 1] (row = label, column = prediction, column C =
+    empty) for the T ``thresholds``.  ``hist``: an int64 buffer of that shape to ACCUMULATE into (a fresh zeroed one
+    otherwise).  No host synchronisation."""
+    logits = _gpu(logits, 'logits')
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        logits = logits.float()
+    c = logits.shape[-1]
+    logits = logits.reshape(-1, c).contiguous()
+    labels = _gpu(labels, 'labels', torch.uint8).reshape(-1)
+    n = logits.shape[0]
+    if labels.numel() != n:
+        raise ValueError('occ_confusion: %d labels for %d logit rows' % (labels.numel(), n))
+    if samples < 1 or n % samples:
+        raise ValueError('occ_confusion: %d rows do not split into %d samples' % (n, samples))
+    thr = [float(t) for t in thresholds]
+    k = c + 1
+    shape = (samples, len(thr), k, k)
+    if hist is None:
+        hist = torch.zeros(shape, dtype=torch.int64, device=logits.device)
+    elif (tuple(hist.shape) != shape or hist.dtype != torch.int64 or not hist.is_contiguous()
+          or hist.device != logits.device):
+        raise ValueError('occ_confusion: hist must be a contiguous int64 %s tensor on %s' % (shape, logits.device))
+    dt = 1 if logits.dtype == torch.bfloat16 else 0
+    host_thr = (ctypes.c_float * max(len(thr), 1))(*thr)
+    _launch('ver_occ_confusion', lambda: lib().ver_occ_confusion(
+        _p(logits), dt, ctypes.c_long(n // samples), samples, c, _p(labels), host_thr, len(thr), _p(hist), _stream()))
+    return hist
 
 
 # ------------------------------------------------------------------------------------------
