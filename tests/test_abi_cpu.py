@@ -1,6 +1,8 @@
 """CPU checks of the drop-in boundary: the C-ABI library builds, loads and exports every
-symbol include/ver_ops.h declares; the Python side fails loudly without a GPU."""
+symbol include/ver_ops.h declares; the Python side binds it with the header's prototypes and fails loudly without a GPU."""
+import ast
 import ctypes
+import glob
 import numpy as np
 import os
 import re
@@ -43,7 +45,7 @@ def test_argument_validation_without_gpu():
     lib = hip.lib()
     rc = lib.ver_msda_forward(None, None, None, None, None, None, 1, 1, 1, 1, 1, 1, 1, 64, None)
     assert rc == -1 and b'null' in lib.ver_last_error()
-    rc = lib.ver_sca_forward(None, 0, None, None, None, None, None, None, None, None, None, 1, 6, 1, 1,
+    rc = lib.ver_sca_forward(None, 0, None, None, None, None, None, None, None, None, None, None, None, 1, 6, 1, 1,
                              8, 96, 8, 14, 14, 0, None)
     assert rc == -1
     rc = lib.ver_sca_zero_rows(None, None, None, 2, 900, 768, None)
@@ -57,7 +59,6 @@ def test_argument_validation_of_the_head_entry_points():
     back as error codes with a message, nothing is launched."""
     hip = pkg('hipops')
     lib = hip.lib()
-    lib.ver_occ_mlp_image_bytes.restype = ctypes.c_long
     assert lib.ver_occ_mlp_image_bytes() == 140 * 1024 and lib.ver_occ_mlp_vector_floats() == 6 * 128 + 16
     buf = (ctypes.c_float * 16)()
     rc = lib.ver_occ_mlp_forward(None, buf, buf, None, ctypes.c_long(4), 64, 16, ctypes.c_float(1e-5), 1, None)
@@ -89,7 +90,6 @@ def test_argument_validation_of_the_gemm_entry_points():
     pure host functions."""
     hip = pkg('hipops')
     lib = hip.lib()
-    lib.ver_wgrad_tn_workspace.restype = ctypes.c_long
     L = ctypes.c_long
     buf = (ctypes.c_float * 64)()
     # the chunk count of the shapes of the 192-viewpoint step (cost model of csrc/ver_wgrad.hip) and its bounds
@@ -187,6 +187,116 @@ def test_argument_validation_of_the_gemm_entry_points():
     assert lib.ver_occ_mlp_forward_stats(None, buf, buf, None, None, L(0), 128, 16, ctypes.c_float(1e-5), 2, None) == 0
     rc = lib.ver_occ_mlp_backward_fused_stats(None, None, None, buf, buf, None, None, buf, L(4), 128, 16, ctypes.c_float(1e-5), None, 2, None)
     assert rc == -1 and b'null' in lib.ver_last_error()
+
+
+# ------------------------------------------------------------------------------------------ the binding (hipops.prototypes)
+def _kinds(params):
+    names = {ctypes.c_void_p: 'pointer', ctypes.c_int: 'int', ctypes.c_long: 'long', ctypes.c_float: 'float'}
+    return {k: [names[p] for p in params].count(k) for k in names.values()}
+
+
+def test_prototypes_are_read_from_the_header():
+    """One prototype per entry point the header declares, and -- for a few entries whose argument lists were counted by
+    eye in include/ver_ops.h -- the right number of parameters of each kind."""
+    hip = pkg('hipops')
+    protos = hip.prototypes()
+    assert sorted(protos) == _declared() and len(protos) >= 63
+    assert tuple(protos) == hip.SYMBOLS
+    ret, params = protos['ver_sca_forward']
+    assert ret is ctypes.c_int and _kinds(params) == dict(pointer=13, int=11, long=0, float=0)
+    ret, params = protos['ver_wgrad_tn_segments_splits']
+    assert ret is ctypes.c_int and params == [ctypes.c_int] * 3 + [ctypes.c_long, ctypes.c_int, ctypes.c_long]
+    kinds = _kinds(protos['ver_focal_loss_forward'][1])
+    assert kinds['float'] == 2 and kinds['long'] == 1 and sum(kinds.values()) == 10
+    assert protos['ver_abi_version'] == (ctypes.c_int, []) and protos['ver_last_error'] == (ctypes.c_char_p, [])
+    assert protos['ver_wgrad_tn_workspace'][0] is ctypes.c_long
+    assert protos['ver_clip_adamw_step_tensors'][1][0] is ctypes.c_void_p                 # `void* const* table`
+    # and that is what the loaded handle carries
+    lib = hip.lib()
+    assert all(list(getattr(lib, name).argtypes) == params for name, (_, params) in protos.items())
+
+
+def test_long_passes_whole_in_and_out_with_plain_python_ints():
+    lib = pkg('hipops').lib()
+    assert lib.ver_focal_loss_blocks(2 ** 33, 16) == 4096          # (N masked to 32 bits would be 0 rows: 1 block)
+    assert lib.ver_focal_loss_blocks(0, 16) == 1
+    assert lib.ver_wgrad_tn_workspace(1000, 4096, 4096, 64) == 64 * 4096 * 4096 * 4 == 2 ** 32       # (0 as a C int)
+
+
+def test_scalar_parameters_take_what_they_should_and_nothing_else():
+    lib = pkg('hipops').lib()
+    # float parameters take a bare Python float (gamma, alpha): the call gets as far as the C % 8 check
+    assert lib.ver_focal_loss_forward(None, None, None, 8, 10, 2.0, .25, 0, None, None) == -2
+    assert b'multiple of 8' in lib.ver_last_error()
+    with pytest.raises(ctypes.ArgumentError):                      # a float where the header says int (C)
+        lib.ver_focal_loss_forward(None, None, None, 8, 10.0, 2.0, .25, 0, None, None)
+    with pytest.raises(ctypes.ArgumentError):                      # ... and where it says long (N)
+        lib.ver_focal_loss_blocks(8.0, 16)
+    # numpy and 0-dim torch integers are integers
+    assert lib.ver_focal_loss_blocks(np.int64(2 ** 33), np.int32(16)) == 4096
+    assert lib.ver_focal_loss_blocks(torch.tensor(2 ** 33), torch.tensor(16, dtype=torch.int32)) == 4096
+    assert lib.ver_wgrad_tn_splits(np.int64(345600), np.int32(14304), torch.tensor(1536)) == 8
+
+
+def test_too_few_arguments_raise():
+    lib = pkg('hipops').lib()
+    short = (None, None, None, None, None, None, 1, 1, 1, 1, 1, 1, 1, 64)          # ver_msda_forward without its stream
+    with pytest.raises(TypeError, match='15 arguments'):
+        lib.ver_msda_forward(*short)               # (starred: the source scan below leaves these two alone)
+    with pytest.raises(TypeError):
+        lib.ver_focal_loss_blocks(*(8,))
+    assert lib.ver_msda_forward(*short, None) == -1
+
+
+def test_a_header_the_parser_cannot_read_is_loud(tmp_path):
+    hip = pkg('hipops')
+    header = tmp_path / 'ver_ops.h'
+
+    def parse(text):
+        header.write_text(text)
+        return hip.prototypes(str(header))
+
+    good = parse('/* int ver_not_this(double x); */\n#define VER_X 1\nint ver_a(const void* p, long n, float f, void* stream);  // int ver_nor_this(\n'
+                 'const char* ver_b(void);\nlong\n  ver_c(int\n a);')
+    assert good == dict(ver_a=(ctypes.c_int, [ctypes.c_void_p, ctypes.c_long, ctypes.c_float, ctypes.c_void_p]),
+                        ver_b=(ctypes.c_char_p, []), ver_c=(ctypes.c_long, [ctypes.c_int]))
+    for bad in ('int ver_a(double x);', 'int ver_a(unsigned n);', 'int ver_a(int);', 'int ver_a(size_t n, void* stream);',
+                'int ver_a();', 'float ver_a(int n);', 'void ver_a(int n);', 'int* ver_a(int n);'):
+        with pytest.raises(hip.HipLibraryError, match='ver_a'):
+            parse('int ver_ok(int n);\n' + bad)
+    for unreadable in ('int ver_a(int n, int (*callback)(int));', 'int ver_a(int n)\nint ver_ok2(void);',
+                       'static inline int ver_a(int n) { return n; }'):
+        with pytest.raises(hip.HipLibraryError, match='ver_a'):
+            parse('int ver_ok(int n);\n' + unreadable)
+    with pytest.raises(hip.HipLibraryError, match='not found'):
+        hip.prototypes(str(tmp_path / 'absent.h'))
+
+
+def _abi_calls(path):
+    """(line, name, number of positional arguments) of every ``<expr>.ver_*(...)`` call without starred arguments."""
+    for node in ast.walk(ast.parse(open(path).read(), path)):
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr.startswith('ver_'):
+            if not any(isinstance(a, ast.Starred) for a in node.args):
+                assert not node.keywords, '%s:%d: a C function takes no keyword arguments' % (path, node.lineno)
+                yield node.lineno, node.func.attr, len(node.args)
+
+
+def test_every_call_site_passes_the_number_of_arguments_the_header_declares():
+    """ctypes rejects a call with too FEW arguments for its prototype, not one with too many (cdecl), and only when the
+    call runs.  This walks the source instead: every ``.ver_*(...)`` call of the package, bench.py and the tests."""
+    protos = pkg('hipops').prototypes()
+    files = (glob.glob(os.path.join(ROOT, 'vln-ver_amd', '**', '*.py'), recursive=True) + [os.path.join(ROOT, 'bench.py')]
+             + glob.glob(os.path.join(ROOT, 'tests', '**', '*.py'), recursive=True))
+    seen, wrong = {}, []
+    for path in files:
+        for line, name, nargs in _abi_calls(path):
+            if name in protos:
+                seen[os.path.relpath(path, ROOT)] = seen.get(os.path.relpath(path, ROOT), 0) + 1
+                if nargs != len(protos[name][1]):
+                    wrong.append('%s:%d: %s takes %d arguments, %d given' % (path, line, name, len(protos[name][1]), nargs))
+    assert not wrong, '\n'.join(wrong)
+    # the scan sees the call sites it is there for
+    assert seen.get(os.path.join('vln-ver_amd', 'hipops.py'), 0) >= 50 and seen.get(os.path.join('vln-ver_amd', 'optim.py'), 0) >= 1
 
 
 class _LatticeStandIn:

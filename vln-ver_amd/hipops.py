@@ -6,6 +6,7 @@ autograd bookkeeping.
 """
 import ctypes
 import os
+import re
 
 import torch
 from torch.autograd import Function
@@ -15,24 +16,41 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # (VER_HIP_LIB: another build of the same ABI, e.g. the host-ASan build libver_hip_asan.so of tests/test_abi_cpu.py)
 LIB_PATH = os.environ.get('VER_HIP_LIB') or os.path.join(_PKG, 'libver_hip.so')
 ABI_VERSION = 30
-SYMBOLS = ('ver_abi_version', 'ver_last_error', 'ver_sca_backward_grad_dtype', 'ver_msda_forward', 'ver_msda_backward',
-           'ver_project_points', 'ver_hits_from_mask', 'ver_sca_zero_rows', 'ver_sca_head_major_supported',
-           'ver_sca_forward', 'ver_sca_backward',
-           'ver_lattice_im2col', 'ver_lattice_col2im', 'ver_ln_relu_forward', 'ver_ln_relu_backward',
-           'ver_msda3d_forward', 'ver_msda3d_backward', 'ver_focal_loss_blocks', 'ver_focal_loss_forward', 'ver_focal_loss_forward_grad', 'ver_focal_loss_forward_grad_u8',
-           'ver_focal_loss_backward', 'ver_occ_mlp_image_bytes', 'ver_occ_mlp_vector_floats', 'ver_occ_mlp_pack',
-           'ver_occ_mlp_forward', 'ver_occ_mlp_backward', 'ver_occ_mlp_backward_fused', 'ver_lattice_gather', 'ver_lattice_scatter',
-           'ver_convt_weight_forward', 'ver_convt_weight_backward', 'ver_convt_weight_backward_blocks', 'ver_convt_weight_forward_blocks', 'ver_blocks_vec_forward', 'ver_blocks_vec_backward', 'ver_lattice_transpose', 'ver_lattice_rows', 'ver_run_gather',
-           'ver_run_scatter', 'ver_add_ln_forward', 'ver_add_ln_backward',
-           'ver_relu_dropout_forward', 'ver_relu_dropout_backward', 'ver_occ_predict_blocks', 'ver_occ_predict', 'ver_occ_confusion',
-           'ver_wgrad_tn_splits', 'ver_wgrad_tn_splits_ld', 'ver_wgrad_tn_segments', 'ver_wgrad_tn_segments_splits', 'ver_wgrad_tn_workspace', 'ver_wgrad_tn', 'ver_occ_mlp_forward_stats',
-           'ver_occ_mlp_backward_fused_stats', 'ver_gemm_nn', 'ver_gemm_nn_splits', 'ver_gemm_nn_splitk', 'ver_gemm_nn_taps', 'ver_gemm_nn_segments', 'ver_gemm_nn_planes', 'ver_clip_adamw_step', 'ver_clip_adamw_step_tensors')
-
-_lib = None
+HEADER = os.path.join(os.path.dirname(_PKG), 'include', 'ver_ops.h')
+_PARAMS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float}
+_RETURNS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'const char*': ctypes.c_char_p}
 
 
 class HipLibraryError(RuntimeError):
     pass
+
+
+def prototypes(path=HEADER):
+    """{name: (return type, parameter types)}, as ctypes, of every ``RET ver_name(ARGS);`` the C header declares.  Exactly
+    the header's grammar: RET is int, long or const char*; a parameter with a ``*`` is a pointer, any other is
+    ``int|long|float name``; ``(void)`` is no parameter.  Anything else raises, as does a ``ver_name(`` that did not
+    parse as a declaration."""
+    if not os.path.exists(path):
+        raise HipLibraryError('%s not found: the C ABI is bound from its prototypes' % path)
+    text = re.sub(r'/\*.*?\*/|//[^\n]*|^\s*#[^\n]*', ' ', open(path).read(), flags=re.S | re.M)
+    out = {}
+    for ret, name, params in re.findall(r'([^;{}()]*?)\b(ver_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', text):
+        ret = _RETURNS.get(' '.join(ret.split()))
+        params = [] if params.strip() == 'void' else [' '.join(q.split()) for q in params.split(',')]
+        args = [ctypes.c_void_p if '*' in q else _PARAMS.get(q.rpartition(' ')[0]) for q in params]
+        if ret is None or None in args:
+            raise HipLibraryError('%s: %s(%s): a type outside int / long / float / pointer' % (path, name, ', '.join(params)))
+        out[name] = (ret, args)
+    unread = set(re.findall(r'\b(ver_[a-z0-9_]+)\s*\(', text)) - set(out)
+    if unread:
+        raise HipLibraryError('%s: no prototype read for %s' % (path, ', '.join(sorted(unread))))
+    return out
+
+
+PROTOTYPES = prototypes()
+SYMBOLS = tuple(PROTOTYPES)
+
+_lib = None
 
 
 def lib():
@@ -44,13 +62,11 @@ def lib():
                 '%s not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                 '(hipcc --offload-arch=gfx950). There is no CPU/PyTorch fallback.' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name in SYMBOLS:
+        for name, (ret, params) in PROTOTYPES.items():
             if not hasattr(handle, name):
                 raise HipLibraryError('%s does not export %s' % (LIB_PATH, name))
-        handle.ver_last_error.restype = ctypes.c_char_p
-        handle.ver_occ_mlp_image_bytes.restype = ctypes.c_long
-        handle.ver_occ_predict_blocks.restype = ctypes.c_long
-        handle.ver_wgrad_tn_workspace.restype = ctypes.c_long
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = ret, params
         if handle.ver_abi_version() != ABI_VERSION:
             raise HipLibraryError('libver_hip.so ABI %d != expected %d: rebuild'
                                   % (handle.ver_abi_version(), ABI_VERSION))
@@ -124,11 +140,13 @@ class timed:
 
 
 def _p(t):
-    return ctypes.c_void_p(t.data_ptr())       # NULL for empty tensors; the C side returns early
+    """Address of a tensor's data for a pointer parameter: None (NULL) for None, 0 (NULL) for an empty tensor, where the
+    C side returns early."""
+    return None if t is None else t.data_ptr()
 
 
 def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _gpu(t, name, dtype=None):
@@ -158,7 +176,7 @@ class MultiScaleDeformableAttnFunction_fp32(Function):
         ctx.im2col_step = im2col_step
         out = value.new_empty(bs, nq, heads * hd)
         _check(lib().ver_msda_forward(_p(value), _p(shapes), _p(lsi), _p(loc), _p(aw), _p(out),
-                                      bs, nk, heads, hd, nl, npt, nq, int(im2col_step), _stream()),
+                                      bs, nk, heads, hd, nl, npt, nq, im2col_step, _stream()),
                'ver_msda_forward')
         ctx.save_for_backward(value, shapes, lsi, loc, aw)
         return out
@@ -176,7 +194,7 @@ class MultiScaleDeformableAttnFunction_fp32(Function):
         go = _gpu(grad_output, 'grad_output').float().contiguous()
         _check(lib().ver_msda_backward(_p(value), _p(shapes), _p(lsi), _p(loc), _p(aw), _p(go),
                                        _p(grad_value), _p(grad_loc), _p(grad_aw), bs, nk, heads, hd,
-                                       nl, npt, nq, int(ctx.im2col_step), _stream()),
+                                       nl, npt, nq, ctx.im2col_step, _stream()),
                'ver_msda_backward')
         return grad_value, None, None, grad_loc, grad_aw, None
 
@@ -220,7 +238,7 @@ def project_points(world2pixel, origin, pc_range, bev_z, bev_h, bev_w, img_w=128
     hit = HitTable(B, ncam, nq, 1, w2p.device)
     rng = (ctypes.c_float * 6)(*[float(v) for v in pc_range])
     _launch('ver_project_points', lambda: lib().ver_project_points(
-        _p(w2p), _p(org), rng, B, ncam, bev_z, bev_h, bev_w, ctypes.c_float(img_w), ctypes.c_float(img_h),
+        _p(w2p), _p(org), rng, B, ncam, bev_z, bev_h, bev_w, img_w, img_h,
         _p(hit.uv), _p(hit.vis), _p(hit.vis_list), _p(hit.vis_cnt), _p(hit.zero_list), _p(hit.zero_cnt),
         _p(hit.fwd_list), _p(hit.fwd_cnt), _stream()))
     return hit
@@ -464,7 +482,7 @@ class ConvTWeightFunction(Function):
         taps = torch.empty(75, ci, co, dtype=dtype, device=weight.device)
         dt = 1 if dtype == torch.bfloat16 else 0
         _launch('ver_convt_weight_forward', lambda: lib().ver_convt_weight_forward(
-            _p(weight), _p(taps), ctypes.c_long(ci * co), dt, _stream()))
+            _p(weight), _p(taps), ci * co, dt, _stream()))
         ctx.shape, ctx.dt, ctx.dtype = tuple(weight.shape), dt, dtype
         return taps
 
@@ -475,7 +493,7 @@ class ConvTWeightFunction(Function):
         ci, co = ctx.shape[:2]
         gw = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
         _launch('ver_convt_weight_backward', lambda: lib().ver_convt_weight_backward(
-            _p(g), _p(gw), ctypes.c_long(ci * co), ctx.dt, _stream()))
+            _p(g), _p(gw), ci * co, ctx.dt, _stream()))
         return gw, None
 
 
@@ -504,8 +522,7 @@ def convt_weight_backward_blocks(blocks, block_offsets, prev_bias, grad_v, ci, c
     gw = torch.empty(ci, co, 3, 5, 5, dtype=torch.float32, device=src.device)
     dt = 1 if src.dtype == torch.bfloat16 else 0
     _launch('ver_convt_weight_backward_blocks', lambda: lib().ver_convt_weight_backward_blocks(
-        _p(src), _p(off), ctypes.c_long(src.stride(0)), _p(prev_bias) if prev_bias is not None else None,
-        _p(grad_v) if grad_v is not None else None, _p(gw), int(ci), int(co), dt, _stream()))
+        _p(src), _p(off), src.stride(0), _p(prev_bias), _p(grad_v), _p(gw), ci, co, dt, _stream()))
     return gw
 
 
@@ -523,7 +540,7 @@ def convt_weight_forward_blocks(weight, block_offsets, blocks, ci, co):
     if off.dtype != torch.int64 or tuple(off.shape) != (75, 2) or not off.is_contiguous():
         raise TypeError('convt_weight_forward_blocks: block_offsets must be a contiguous int64 [75, 2]')
     _launch('ver_convt_weight_forward_blocks', lambda: lib().ver_convt_weight_forward_blocks(
-        _p(w), _p(off), ctypes.c_long(dst.stride(0)), _p(dst), int(ci), int(co), 1 if dst.dtype == torch.bfloat16 else 0, _stream()))
+        _p(w), _p(off), dst.stride(0), _p(dst), ci, co, 1 if dst.dtype == torch.bfloat16 else 0, _stream()))
     return blocks
 
 
@@ -546,7 +563,7 @@ def blocks_vec_forward(blocks, block_rows, ci, x):
         raise ValueError('blocks_vec_forward: x must have Ci elements')
     part = torch.empty(8, rows.numel(), src.shape[1], dtype=torch.float32, device=src.device)      # 8 slices of ci
     _launch('ver_blocks_vec_forward', lambda: lib().ver_blocks_vec_forward(
-        _p(src), _p(rows), int(rows.numel()), ctypes.c_long(src.stride(0)), int(ci), int(src.shape[1]), _p(x), _p(part),
+        _p(src), _p(rows), rows.numel(), src.stride(0), ci, src.shape[1], _p(x), _p(part),
         1 if src.dtype == torch.bfloat16 else 0, _stream()))
     return part.sum(0)
 
@@ -559,7 +576,7 @@ def blocks_vec_backward(blocks, block_rows, ci, grad_vec):
         raise ValueError('blocks_vec_backward: grad_vec must be [nblocks, ncols]')
     part = torch.empty(rows.numel(), ci, dtype=torch.float32, device=src.device)                     # one row per block
     _launch('ver_blocks_vec_backward', lambda: lib().ver_blocks_vec_backward(
-        _p(src), _p(rows), int(rows.numel()), ctypes.c_long(src.stride(0)), int(ci), int(src.shape[1]), _p(gv), _p(part),
+        _p(src), _p(rows), rows.numel(), src.stride(0), ci, src.shape[1], _p(gv), _p(part),
         1 if src.dtype == torch.bfloat16 else 0, _stream()))
     return part.sum(0)
 
@@ -591,8 +608,7 @@ def lattice_transpose(channels_last, channel_first, combined_hw, layout, to_chan
     B, Z, C = _lattice_dims(cl, int(layout))
     dt = 1 if cl.dtype == torch.bfloat16 else 0
     _launch('ver_lattice_transpose', lambda: lib().ver_lattice_transpose(
-        _p(cl), _p(cf), ctypes.c_long(cf.shape[1]), B, Z, H, W, C, int(layout), int(to_channel_first), dt,
-        _stream()))
+        _p(cl), _p(cf), cf.shape[1], B, Z, H, W, C, layout, to_channel_first, dt, _stream()))
 
 
 def lattice_rows(channels_last, rows, row_map, combined_hw, layout, to_rows):
@@ -611,8 +627,8 @@ def lattice_rows(channels_last, rows, row_map, combined_hw, layout, to_rows):
     ints = lambda k: (ctypes.c_int * n)(*[int(v) for v in row_map[k]])
     base = (ctypes.c_long * n)(*[int(v) for v in row_map['seg_base']])
     _launch('ver_lattice_rows', lambda: lib().ver_lattice_rows(
-        _p(cl), _p(buf), ctypes.c_long(int(row_map['quarter'])), int(row_map['period']), n, ints('seg_off'), ints('seg_len'),
-        base, ints('seg_pitch'), ints('seg_rows'), B, Z, H, W, C, int(layout), int(to_rows), 1, _stream()))
+        _p(cl), _p(buf), row_map['quarter'], row_map['period'], n, ints('seg_off'), ints('seg_len'),
+        base, ints('seg_pitch'), ints('seg_rows'), B, Z, H, W, C, layout, to_rows, 1, _stream()))
 
 
 def run_gather(image, run_start, aug_idx, rows, n_rows, run_len):
@@ -626,8 +642,8 @@ def run_gather(image, run_start, aug_idx, rows, n_rows, run_len):
     B = img.shape[0]
     runs, n_aug = run_start.shape[1], aug_idx.shape[1]
     _launch('ver_run_gather', lambda: lib().ver_run_gather(
-        _p(img), ctypes.c_long(img.shape[1]), _p(run_start), _p(aug_idx), _p(out), B, n_rows, runs, run_len, n_aug,
-        out.shape[1], 1 if img.dtype == torch.bfloat16 else 0, _stream()))
+        _p(img), img.shape[1], _p(run_start), _p(aug_idx), _p(out), B, n_rows, runs, run_len, n_aug, out.shape[1],
+        1 if img.dtype == torch.bfloat16 else 0, _stream()))
 
 
 def run_scatter(rows, image, run_start, n_rows, run_len):
@@ -639,7 +655,7 @@ def run_scatter(rows, image, run_start, n_rows, run_len):
         raise TypeError('run_scatter: fp32 or bf16')
     B = img.shape[0]
     _launch('ver_run_scatter', lambda: lib().ver_run_scatter(
-        _p(src), _p(img), ctypes.c_long(img.shape[1]), _p(run_start), B, n_rows, run_start.shape[1], run_len,
+        _p(src), _p(img), img.shape[1], _p(run_start), B, n_rows, run_start.shape[1], run_len,
         src.shape[1], 1 if img.dtype == torch.bfloat16 else 0, _stream()))
 
 
@@ -669,8 +685,7 @@ def lattice_gather(src, col, taps, col_offset, combined_hw, layout, row_z=None, 
         nblk, cw = int(const_rows.shape[1]), int(const_rows.shape[2])
         cptr, coffs = _p(const_rows), (ctypes.c_long * nblk)(*[int(o) for o in const_offset])
     _launch('ver_lattice_gather', lambda: lib().ver_lattice_gather(
-        _p(src), _p(col), arr, offs, ctypes.c_long(col.shape[1]), len(taps), B, Zr, Zs, H, W, C, int(layout), dt,
-        cptr, coffs, nblk, cw, _stream()))
+        _p(src), _p(col), arr, offs, col.shape[1], len(taps), B, Zr, Zs, H, W, C, layout, dt, cptr, coffs, nblk, cw, _stream()))
     return col
 
 
@@ -685,8 +700,7 @@ def lattice_scatter(grad_col, grad_src, taps, col_offset, combined_hw, layout, r
     arr, offs = _tap_args(taps, col_offset)
     dt = 1 if grad_src.dtype == torch.bfloat16 else 0
     _launch('ver_lattice_scatter', lambda: lib().ver_lattice_scatter(
-        _p(grad_col), _p(grad_src), arr, offs, ctypes.c_long(grad_col.shape[1]), len(taps), B, Zr, Zs, H, W, C,
-        int(layout), dt, _stream()))
+        _p(grad_col), _p(grad_src), arr, offs, grad_col.shape[1], len(taps), B, Zr, Zs, H, W, C, layout, dt, _stream()))
     return grad_src
 
 
@@ -709,8 +723,7 @@ class LayerNormReluFunction(Function):
         mean = torch.empty(n, dtype=torch.float32, device=x.device)
         rstd = torch.empty(n, dtype=torch.float32, device=x.device)
         _launch('ver_ln_relu_forward', lambda: lib().ver_ln_relu_forward(
-            _p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), ctypes.c_long(n), w,
-            ctypes.c_float(eps), dt, _stream()))
+            _p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), n, w, eps, dt, _stream()))
         ctx.save_for_backward(x, gamma, beta, mean, rstd)
         ctx.dt = dt
         return y
@@ -726,8 +739,7 @@ class LayerNormReluFunction(Function):
         gg = torch.empty(w, dtype=torch.float32, device=x.device)
         gb = torch.empty(w, dtype=torch.float32, device=x.device)
         _launch('ver_ln_relu_backward', lambda: lib().ver_ln_relu_backward(
-            _p(x), _p(gy), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(gx), _p(gg), _p(gb),
-            ctypes.c_long(n), w, ctx.dt, _stream()))
+            _p(x), _p(gy), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(gx), _p(gg), _p(gb), n, w, ctx.dt, _stream()))
         return gx, gg, gb, None
 
 
@@ -804,13 +816,12 @@ class SigmoidFocalLossSumFunction(Function):
         if target.shape != (n,):
             raise ValueError('target must be [N]')
         dt = 1 if logits.dtype == torch.bfloat16 else 0
-        blocks = lib().ver_focal_loss_blocks(ctypes.c_long(n), c)
+        blocks = lib().ver_focal_loss_blocks(n, c)
         partial = torch.zeros(blocks, dtype=torch.float32, device=logits.device)
         flag = LabelRangeFlag.of(logits.device)
         flag.poll()                                          # a bad label of an EARLIER call is reported here
         _launch('ver_focal_loss_forward', lambda: lib().ver_focal_loss_forward(
-            _p(logits), _p(target), _p(partial), ctypes.c_long(n), c, ctypes.c_float(gamma),
-            ctypes.c_float(alpha), dt, _p(flag.dev), _stream()))
+            _p(logits), _p(target), _p(partial), n, c, gamma, alpha, dt, _p(flag.dev), _stream()))
         flag.mirror(c)
         ctx.save_for_backward(logits, target)
         ctx.cfg = (gamma, alpha, dt)
@@ -825,8 +836,7 @@ class SigmoidFocalLossSumFunction(Function):
         scale = _gpu(grad_out, 'grad_out').float().reshape(1).contiguous()
         grad = torch.empty_like(logits)
         _launch('ver_focal_loss_backward', lambda: lib().ver_focal_loss_backward(
-            _p(logits), _p(target), _p(scale), _p(grad), ctypes.c_long(n), c, ctypes.c_float(gamma),
-            ctypes.c_float(alpha), dt, _stream()))
+            _p(logits), _p(target), _p(scale), _p(grad), n, c, gamma, alpha, dt, _stream()))
         return grad, None, None, None
 
 
@@ -870,8 +880,8 @@ def occ_mlp_forward(x, image, vectors, eps=1e-5, first_linear=True, centered=Fal
     logits = torch.empty(x.shape[:-1] + (16,), dtype=torch.bfloat16, device=x.device)
     rstd = torch.empty(n, 2, dtype=torch.float32, device=x.device) if want_rstd else None
     _launch('ver_occ_mlp_forward', lambda: lib().ver_occ_mlp_forward_stats(
-        _p(x), _p(image), _p(vectors), _p(logits), _p(rstd) if rstd is not None else None, ctypes.c_long(n), 128, 16,
-        ctypes.c_float(eps), (1 if first_linear else 0) | (2 if centered else 0), _stream()))
+        _p(x), _p(image), _p(vectors), _p(logits), _p(rstd), n, 128, 16, eps,
+        (1 if first_linear else 0) | (2 if centered else 0), _stream()))
     return (logits, rstd) if want_rstd else logits
 
 
@@ -967,9 +977,7 @@ class OccMLPFunction(Function):
             pg = torch.empty(6 * 128 + 16 * 128 + 16 + 128 * 128, dtype=torch.float32, device=x.device)
             _launch('ver_occ_mlp_backward_fused', lambda: lib().ver_occ_mlp_backward_fused_stats(
                 _p(x2), _p(gl), _p(w2.float().contiguous()), _p(w3.float().contiguous()), _p(vec),
-                _p(rstd) if rstd is not None else None, _p(gx), _p(pg),
-                ctypes.c_long(n), 128, 16, ctypes.c_float(ctx.eps), _p(gscale) if gscale is not None else None,
-                2 if ctx.centered else 0, _stream()))
+                _p(rstd), _p(gx), _p(pg), n, 128, 16, ctx.eps, _p(gscale), 2 if ctx.centered else 0, _stream()))
             vecs = pg[:768].view(6, 128)
             dw3 = pg[768:768 + 2048].view(16, 128)
             db3 = pg[768 + 2048:768 + 2048 + 16]
@@ -979,8 +987,8 @@ class OccMLPFunction(Function):
         ga1 = None if ctx.folded else torch.empty_like(x2)
         pg = torch.empty(6 * 128 + 16 * 128 + 16, dtype=torch.float32, device=x.device)
         _launch('ver_occ_mlp_backward', lambda: lib().ver_occ_mlp_backward(
-            _p(x2), _p(gl), _p(image), _p(vec), _p(gx), _p(ga1) if ga1 is not None else None, _p(ga2), _p(h1), _p(pg),
-            ctypes.c_long(n), 128, 16, ctypes.c_float(ctx.eps), 0 if ctx.folded else 1, _stream()))
+            _p(x2), _p(gl), _p(image), _p(vec), _p(gx), _p(ga1), _p(ga2), _p(h1), _p(pg),
+            n, 128, 16, ctx.eps, 0 if ctx.folded else 1, _stream()))
         inv = _frag_order(x.device)
         vecs = pg[:768].view(6, 128)
         dw3 = pg[768:768 + 2048].view(16, 128)
@@ -1017,14 +1025,13 @@ class OccMLPFocalLossFunction(Function):
         target = (target if as_bytes else target.to(torch.int64)).contiguous()
         if target.shape != (n,):
             raise ValueError('target must be [N]')
-        blocks = lib().ver_focal_loss_blocks(ctypes.c_long(n), 16)
+        blocks = lib().ver_focal_loss_blocks(n, 16)
         partial = torch.zeros(blocks, dtype=torch.float32, device=x.device)
         flag = LabelRangeFlag.of(x.device)
         flag.poll()
         entry = lib().ver_focal_loss_forward_grad_u8 if as_bytes else lib().ver_focal_loss_forward_grad
         _launch('ver_focal_loss_forward_grad', lambda: entry(
-            _p(l2), _p(target), _p(partial), _p(l2), ctypes.c_long(n), 16, ctypes.c_float(gamma), ctypes.c_float(alpha),
-            1, _p(flag.dev), _stream()))                      # (in place: the logits buffer now holds d loss / d logits)
+            _p(l2), _p(target), _p(partial), _p(l2), n, 16, gamma, alpha, 1, _p(flag.dev), _stream()))                      # (in place: the logits buffer now holds d loss / d logits)
         flag.mirror(16)
         ctx.save_for_backward(x, vec, w2.detach(), w3.detach(), l2, *((rstd,) if ctx.has_rstd else ()))
         ctx.eps, ctx.centered = eps, bool(centered)
@@ -1043,8 +1050,7 @@ class OccMLPFocalLossFunction(Function):
         pg = torch.empty(6 * 128 + 16 * 128 + 16 + 128 * 128, dtype=torch.float32, device=x.device)
         _launch('ver_occ_mlp_backward_fused', lambda: lib().ver_occ_mlp_backward_fused_stats(
             _p(x2), _p(gl), _p(w2.float().contiguous()), _p(w3.float().contiguous()), _p(vec),
-            _p(rstd) if rstd is not None else None, _p(gx), _p(pg),
-            ctypes.c_long(n), 128, 16, ctypes.c_float(ctx.eps), _p(gscale), 2 if ctx.centered else 0, _stream()))
+            _p(rstd), _p(gx), _p(pg), n, 128, 16, ctx.eps, _p(gscale), 2 if ctx.centered else 0, _stream()))
         vecs = pg[:768].view(6, 128)
         dw3 = pg[768:768 + 2048].view(16, 128)
         db3 = pg[768 + 2048:768 + 2048 + 16]
@@ -1083,9 +1089,8 @@ class AddDropoutLayerNormFunction(Function):
         seed = torch.randint(0, 2 ** 62, (1,), device=res.device, dtype=torch.int64) if p_drop > 0 else None
         g, b = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
         _launch('ver_add_ln_forward', lambda: lib().ver_add_ln_forward(
-            _p(a), 1 if a.dtype == torch.bfloat16 else 0, _p(res), _p(g), _p(b), _p(seed) if seed is not None else None,
-            ctypes.c_float(p_drop), ctypes.c_float(eps), _p(y), _p(y16) if y16 is not None else None, _p(mean), _p(rstd),
-            ctypes.c_long(n), C, _stream()))
+            _p(a), 1 if a.dtype == torch.bfloat16 else 0, _p(res), _p(g), _p(b), _p(seed), p_drop, eps, _p(y), _p(y16),
+            _p(mean), _p(rstd), n, C, _stream()))
         ctx.save_for_backward(a, res, g, mean, rstd, seed if seed is not None else torch.empty(0, device=res.device))
         ctx.p_drop, ctx.has_y16 = p_drop, want_bf16
         if want_bf16:
@@ -1107,9 +1112,8 @@ class AddDropoutLayerNormFunction(Function):
         dg = torch.empty(C, dtype=torch.float32, device=res.device)
         db = torch.empty_like(dg)
         _launch('ver_add_ln_backward', lambda: lib().ver_add_ln_backward(
-            _p(gy), _p(gy16) if gy16 is not None else None, _p(a), 1 if a.dtype == torch.bfloat16 else 0, _p(res), _p(g),
-            _p(mean), _p(rstd), _p(seed) if ctx.p_drop > 0 else None, ctypes.c_float(ctx.p_drop), _p(d_a), _p(d_res),
-            _p(dg), _p(db), ctypes.c_long(n), C, _stream()))
+            _p(gy), _p(gy16), _p(a), 1 if a.dtype == torch.bfloat16 else 0, _p(res), _p(g), _p(mean), _p(rstd),
+            _p(seed) if ctx.p_drop > 0 else None, ctx.p_drop, _p(d_a), _p(d_res), _p(dg), _p(db), n, C, _stream()))
         return d_a, d_res, dg, db, None, None, None
 
 
@@ -1125,8 +1129,7 @@ class ReluDropoutFunction(Function):
         y = torch.empty_like(x)
         seed = torch.randint(0, 2 ** 62, (1,), device=x.device, dtype=torch.int64) if p_drop > 0 else None
         _launch('ver_relu_dropout_forward', lambda: lib().ver_relu_dropout_forward(
-            _p(x), _p(y), _p(seed) if seed is not None else None, ctypes.c_float(p_drop), ctypes.c_long(x.numel()),
-            1 if x.dtype == torch.bfloat16 else 0, _stream()))
+            _p(x), _p(y), _p(seed), p_drop, x.numel(), 1 if x.dtype == torch.bfloat16 else 0, _stream()))
         ctx.save_for_backward(y)
         ctx.p_drop = p_drop
         return y
@@ -1138,8 +1141,7 @@ class ReluDropoutFunction(Function):
         gy = _gpu(grad_y, 'grad_y').to(y.dtype).contiguous()
         gx = torch.empty_like(y)
         _launch('ver_relu_dropout_backward', lambda: lib().ver_relu_dropout_backward(
-            _p(y), _p(gy), _p(gx), ctypes.c_float(ctx.p_drop), ctypes.c_long(y.numel()),
-            1 if y.dtype == torch.bfloat16 else 0, _stream()))
+            _p(y), _p(gy), _p(gx), ctx.p_drop, y.numel(), 1 if y.dtype == torch.bfloat16 else 0, _stream()))
         return gx, None
 
 
@@ -1203,12 +1205,12 @@ def occ_predict(logits, threshold=0.25):
     logits = logits.contiguous()
     n, c = logits.shape
     dt = 1 if logits.dtype == torch.bfloat16 else 0
-    nb = lib().ver_occ_predict_blocks(ctypes.c_long(n))
+    nb = lib().ver_occ_predict_blocks(n)
     work = torch.empty(max(nb, 1), dtype=torch.int32, device=logits.device)
     pairs = torch.empty(max(n, 1), 2, dtype=torch.int64, device=logits.device)
     count = torch.empty(1, dtype=torch.int64, device=logits.device)
     _launch('ver_occ_predict', lambda: lib().ver_occ_predict(
-        _p(logits), dt, ctypes.c_long(n), c, ctypes.c_float(threshold), _p(work), _p(pairs), _p(count), _stream()))
+        _p(logits), dt, n, c, threshold, _p(work), _p(pairs), _p(count), _stream()))
     return pairs[:int(count.item())]
 
 
@@ -1240,7 +1242,7 @@ def occ_confusion(logits, labels, thresholds=(0.25,), samples=1, hist=None):
     dt = 1 if logits.dtype == torch.bfloat16 else 0
     host_thr = (ctypes.c_float * max(len(thr), 1))(*thr)
     _launch('ver_occ_confusion', lambda: lib().ver_occ_confusion(
-        _p(logits), dt, ctypes.c_long(n // samples), samples, c, _p(labels), host_thr, len(thr), _p(hist), _stream()))
+        _p(logits), dt, n // samples, samples, c, _p(labels), host_thr, len(thr), _p(hist), _stream()))
     return hist
 
 
@@ -1266,17 +1268,16 @@ def wgrad_tn(a, g, out_dtype=None, splits=0, flags=0, out=None):
         raise TypeError('wgrad_tn: out_dtype must be bf16 or fp32')
     L = lib()
     if splits <= 0:
-        splits = L.ver_wgrad_tn_splits_ld(ctypes.c_long(m), ka, n, ctypes.c_long(max(a.stride(0), g.stride(0))))
-    nbytes = L.ver_wgrad_tn_workspace(ctypes.c_long(m), ka, n, splits)
+        splits = L.ver_wgrad_tn_splits_ld(m, ka, n, max(a.stride(0), g.stride(0)))
+    nbytes = L.ver_wgrad_tn_workspace(m, ka, n, splits)
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=a.device)
     if out is None:
         out = torch.empty(ka, n, dtype=out_dtype, device=a.device)
     elif not (out.is_cuda and out.shape == (ka, n) and out.dtype == out_dtype and out.stride(1) == 1):
         raise RuntimeError('wgrad_tn: out must be a [Ka, N] GPU matrix of out_dtype with unit column stride')
     _launch('ver_wgrad_tn', lambda: L.ver_wgrad_tn(
-        _p(a), ctypes.c_long(a.stride(0)), _p(g), ctypes.c_long(g.stride(0)), ctypes.c_long(m), ka, n, _p(out),
-        ctypes.c_long(out.stride(0)), 1 if out_dtype == torch.bfloat16 else 0, int(splits), int(flags), _p(ws), ctypes.c_long(nbytes),
-        _stream()), meta=dict(flops=2.0 * m * ka * n))
+        _p(a), a.stride(0), _p(g), g.stride(0), m, ka, n, _p(out), out.stride(0), 1 if out_dtype == torch.bfloat16 else 0,
+        splits, flags, _p(ws), nbytes, _stream()), meta=dict(flops=2.0 * m * ka * n))
     return out
 
 
@@ -1290,7 +1291,7 @@ def gemm_nn_supported(a, w):
 
 def gemm_nn_splits(m, k, n):
     """K slices ``gemm_nn`` would cut an [m, k] x [k, n] product into (1: one pass, no workspace): > 1 for skinny operands."""
-    return int(lib().ver_gemm_nn_splits(ctypes.c_long(m), int(k), int(n)))
+    return lib().ver_gemm_nn_splits(m, k, n)
 
 
 def gemm_nn(a, w, bias=None, out=None, splits=None, timer_class='ver_gemm_nn'):
@@ -1314,9 +1315,8 @@ def gemm_nn(a, w, bias=None, out=None, splits=None, timer_class='ver_gemm_nn'):
         splits = 1
     ws = torch.empty(splits * m * n, dtype=torch.float32, device=a.device) if splits > 1 else None
     _launch(timer_class, lambda: lib().ver_gemm_nn_splitk(
-        _p(a), ctypes.c_long(a.stride(0)), _p(w), ctypes.c_long(w.stride(0)), _p(bias) if bias is not None else None,
-        _p(out), ctypes.c_long(out.stride(0)), ctypes.c_long(m), k, n, int(splits), _p(ws) if ws is not None else None,
-        ctypes.c_long(ws.numel() * 4 if ws is not None else 0), _stream()), meta=dict(flops=2.0 * m * k * n))
+        _p(a), a.stride(0), _p(w), w.stride(0), _p(bias), _p(out), out.stride(0), m, k, n, splits, _p(ws),
+        ws.numel() * 4 if ws is not None else 0, _stream()), meta=dict(flops=2.0 * m * k * n))
     return out
 
 
@@ -1377,10 +1377,8 @@ def gemm_nn_taps(lattice, layout, combined_hw, taps, w, rowpos=None, bias=None, 
     arr = (ctypes.c_int * len(flat))(*flat)
     parr = (ctypes.c_int * len(taps))(*[int(v) for v in planes]) if planes is not None else None
     _launch(timer_class, lambda: lib().ver_gemm_nn_planes(
-        _p(lat), int(layout), int(B), int(H), int(W), int(C), ctypes.c_long(plane_elems), nplanes, parr, arr, len(taps),
-        _p(const_rows) if const_rows is not None else None,
-        ncst, cw, _p(w), ctypes.c_long(w.stride(0)), _p(rowpos) if rowpos is not None else None, _p(bias) if bias is not None else None, _p(out), ctypes.c_long(out.stride(0)),
-        int(n), _stream()), meta=dict(flops=2.0 * m * w.shape[0] * n))
+        _p(lat), layout, B, H, W, C, plane_elems, nplanes, parr, arr, len(taps), _p(const_rows), ncst, cw, _p(w), w.stride(0),
+        _p(rowpos), _p(bias), _p(out), out.stride(0), n, _stream()), meta=dict(flops=2.0 * m * w.shape[0] * n))
     return out
 
 
@@ -1433,10 +1431,9 @@ def wgrad_tn_segments(lattice, layout, combined_hw, taps, g, out_dtype=None, out
         raise RuntimeError('wgrad_tn_segments: out must be a [Ka, N] GPU matrix of out_dtype with unit column stride')
     L = lib()
     if splits <= 0:
-        splits = L.ver_wgrad_tn_segments_splits(int(B), int(H), int(W), ctypes.c_long(ka), int(n), ctypes.c_long(g.stride(0)))
+        splits = L.ver_wgrad_tn_segments_splits(B, H, W, ka, n, g.stride(0))
     ws = torch.empty(splits * ka * n, dtype=torch.float32, device=lat.device)
     _launch('ver_wgrad_tn', lambda: L.ver_wgrad_tn_segments(
-        _p(lat), int(layout), int(B), int(H), int(W), int(C), arr, nseg, _p(const_rows) if const_rows is not None else None, ncst, cw,
-        _p(g), ctypes.c_long(g.stride(0)), int(n), _p(out), ctypes.c_long(out.stride(0)), 1 if out_dtype == torch.bfloat16 else 0,
-        int(splits), _p(ws), ctypes.c_long(ws.numel() * 4), _stream()), meta=dict(flops=2.0 * g.shape[0] * ka * n))
+        _p(lat), layout, B, H, W, C, arr, nseg, _p(const_rows), ncst, cw, _p(g), g.stride(0), n, _p(out), out.stride(0),
+        1 if out_dtype == torch.bfloat16 else 0, splits, _p(ws), ws.numel() * 4, _stream()), meta=dict(flops=2.0 * g.shape[0] * ka * n))
     return out

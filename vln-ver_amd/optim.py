@@ -18,7 +18,6 @@ every call: a changed gradient / moment / parameter pointer (``zero_grad(set_to_
 ``model.to()``), a changed lr (schedulers) or a step count that was set from outside is uploaded again before the launch --
 nothing is cached by object identity.
 """
-import ctypes
 
 import numpy as np
 import torch
@@ -152,8 +151,8 @@ class ClipAdamW(torch.optim.Optimizer):
         L = hipops.lib()
         hipops._launch('ver_clip_adamw_step', lambda: L.ver_clip_adamw_step_tensors(
             hipops._p(d['table']), hipops._p(sizes), hipops._p(chunk_tensor), hipops._p(chunk_index), hipops._p(d['hyper_dev']),
-            hipops._p(d['steps_dev']), n, int(chunk_tensor.numel()), self.CHUNK, hipops._p(partial), hipops._p(norm),
-            ctypes.c_float(max_norm), hipops._stream()))
+            hipops._p(d['steps_dev']), n, chunk_tensor.numel(), self.CHUNK, hipops._p(partial), hipops._p(norm), max_norm,
+            hipops._stream()))
         if capturing:
             # nothing has run: the replays advance the device counts, ``replayed()`` the host's
             self._captured = states
