@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define VER_ABI_VERSION 30
+#define VER_ABI_VERSION 31
 
 #define VER_OK            0
 #define VER_EINVAL       -1   /* bad argument (null pointer, non-positive size, ...) */
@@ -593,6 +593,28 @@ int ver_clip_adamw_step(void* const* table, const long* sizes, const int* chunk_
 int ver_clip_adamw_step_tensors(void* const* table, const long* sizes, const int* chunk_tensor, const int* chunk_index,
                                 const float* hyper, int* steps, int n_tensors, int n_chunks, int chunk_elems, float* partial,
                                 float* norm_out, float max_norm, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Hungarian target assignment (ABI 31): a batch of rectangular linear sum assignment problems, with the semantics of
+ * `scipy.optimize.linear_sum_assignment(cost[p, :, :ncols[p]])` as the reference calls it per (decoder layer, sample) at
+ * core/bbox/assigners/hungarian_assigner_3d.py:129 (detection boxes) and :165 (room layout) -- on the device, so that the
+ * targets of a training step need no device -> host round trip and can be part of a captured graph.
+ *   cost   f32 [P, R, Ccap]  (row pitch Ccap; columns >= ncols[p] of problem p are never read)
+ *   ncols  i32 device [P]    valid columns of problem p, 0 <= ncols[p] <= Ccap
+ *   match  i32 [P, R]        written in full: the column assigned to row r, or -1
+ *   bad    i32 device scalar or NULL: 1 is ORed in when a problem holds a NaN or -inf among its valid entries, or has no
+ *          finite assignment (scipy raises on both), or its ncols lies outside [0, Ccap]; that problem's rows are all -1.
+ *          Never cleared by the kernel.
+ * min(R, ncols[p]) rows are matched and the total cost is minimal; either side may be the longer one.  +inf entries are
+ * legal ("this pair is forbidden").  Shortest augmenting paths (Jonker-Volgenant / Crouse 2016, scipy's algorithm) on the
+ * orientation with fewer rows, duals and path costs in fp64 and in scipy's order of operations: with fp32 costs and a UNIQUE
+ * optimum the result is scipy's, index for index.  Among several optima of equal total cost the choice may differ from
+ * scipy's (tie rule of a search step: smallest path cost, then an unassigned column, then the lowest index).
+ * One wavefront per problem (csrc/ver_assign.hip).  Supported: 1 <= R <= 1024, 0 <= Ccap <= 1024 (VER_EUNSUPPORTED beyond),
+ * any P >= 0; P == 0 launches nothing, ncols[p] == 0 gives all -1.  One kernel launch, no memset node, no allocation.
+ */
+int ver_lsa_solve(const float* cost, const int32_t* ncols, int32_t* match, int32_t* bad,
+                  int P, int R, int Ccap, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,8 +3,9 @@
 ``HungarianAssigner3D`` / ``BBox3DL1Cost`` follow the reference's
 core/bbox/assigners/hungarian_assigner_3d.py:16-143 and core/bbox/match_costs/match_cost.py:5-27;
 ``FocalLossCost`` / ``IoUCost`` / the pseudo sampler are restated from mmdet 2.14.0 (SURVEY.md
-B.12).  The matching itself stays on the host (scipy ``linear_sum_assignment`` on a 100 x G cost
-matrix), as in the reference."""
+B.12).  By default the matching itself stays on the host (scipy ``linear_sum_assignment`` on a 100 x G cost
+matrix), as in the reference; ``HungarianAssigner3D(solver='device')`` solves it with ``hipops.lsa_solve`` instead
+(no device -> host round trip; among several optima of EQUAL cost its choice may differ from scipy's)."""
 import torch
 
 from ..registry import BBOX_ASSIGNERS, MATCH_COST, build_from_cfg
@@ -67,7 +68,10 @@ class SamplingResult:
 class HungarianAssigner3D:
     def __init__(self, cls_cost=dict(type='ClassificationCost', weight=1.),
                  reg_cost=dict(type='BBoxL1Cost', weight=1.0), iou_cost=dict(type='IoUCost', weight=0.0),
-                 pc_range=None):
+                 pc_range=None, solver='host'):
+        if solver not in ('host', 'device'):
+            raise ValueError("HungarianAssigner3D: solver must be 'host' or 'device', got %r" % (solver,))
+        self.solver = solver
         self.cls_cost = build_from_cfg(cls_cost, MATCH_COST)
         self.reg_cost = build_from_cfg(reg_cost, MATCH_COST)
         self.iou_cost = build_from_cfg(iou_cost, MATCH_COST)
@@ -84,6 +88,8 @@ class HungarianAssigner3D:
             return AssignResult(num_gts, gt_inds, None, labels=labels)
         reg_cost = self.reg_cost(bbox_pred[:, :8], normalize_bbox(gt_bboxes, self.pc_range)[:, :8])
         cost = reg_cost if layout else self.cls_cost(cls_pred, gt_labels) + reg_cost
+        if self.solver == 'device' and cost.is_cuda:
+            return self._assign_on_device(cost.detach().float(), num_gts, gt_labels)
         if linear_sum_assignment is None:
             raise ImportError('Please run "pip install scipy" to install scipy first.')
         rows, cols = linear_sum_assignment(cost.detach().float().cpu())
@@ -92,6 +98,22 @@ class HungarianAssigner3D:
         gt_inds[:] = 0
         gt_inds[rows] = cols + 1
         labels[rows] = gt_labels if gt_labels.dim() < 1 else gt_labels[cols]
+        return AssignResult(num_gts, gt_inds, None, labels=labels)
+
+    @staticmethod
+    def _assign_on_device(cost, num_gts, gt_labels):
+        """The one problem of ``assign`` through ``lsa_solve``: nothing is copied to the host (a problem scipy would raise on
+        -- NaN / -inf costs, no finite assignment -- leaves every query unmatched and is reported by a later call)."""
+        from ..hipops import AssignmentFlag, lsa_solve
+        flag = AssignmentFlag.of(cost.device)
+        flag.poll()
+        ncols = torch.full((1,), num_gts, dtype=torch.int32, device=cost.device)
+        match = lsa_solve(cost[None], ncols, bad=flag.dev)[0].long()
+        flag.mirror(None)
+        matched = match >= 0
+        gt_inds = match + 1
+        per_gt = (gt_labels if gt_labels.dim() else gt_labels.expand(num_gts)).long()
+        labels = torch.where(matched, per_gt[match.clamp(min=0)], torch.full_like(match, -1))
         return AssignResult(num_gts, gt_inds, None, labels=labels)
 
 

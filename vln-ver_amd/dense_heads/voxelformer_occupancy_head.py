@@ -12,6 +12,7 @@ What differs is how the occupancy branch is evaluated:
 * the raw ``.view`` re-interpretations of :558 and :564 are kept exactly (they are part of the
   reference's results), per sample, so any batch size works (the reference is bs=1 only).
 """
+import collections
 import contextlib
 import copy
 import math
@@ -41,6 +42,11 @@ def _mean_over_ranks(value, like):
     if not (dist.is_available() and dist.is_initialized()):
         return float(value)
     return float(reduce_mean(like.new_tensor([float(value)])))
+
+
+# Ground truth of a batch in static shapes (``VoxelFormerOccupancyHead.pad_gts``), all on the device: boxes [bs, cap, 9]
+# (gravity centre, dims, yaw, zero velocity; rows >= counts[b] are padding), labels int64 [bs, cap], counts int32 [bs].
+PaddedGts = collections.namedtuple('PaddedGts', 'boxes labels counts')
 
 
 def _to_device_async(t, dev):
@@ -549,9 +555,11 @@ class VoxelFormerOccupancyHead(BaseModule):
         # (the branches above only read the decoder states: they run BEFORE the occupancy head -- the reference runs them
         #  after it, head:584-613, same results -- so that a training step can start its Hungarian assignment early:
         #  ``targets_for=(gt_bboxes_list, gt_labels_list)`` queues the cost matrices and their device -> host copy here, the
-        #  host solves them while the GPU is busy with the occupancy head below, and ``loss`` picks the result up)
+        #  host solves them while the GPU is busy with the occupancy head below, and ``loss`` picks the result up; with the
+        #  assigner's solver='device' there is nothing to start early: ``loss`` only queues launches)
         pending = None
-        if targets_for is not None and not self.add_layout and not torch.cuda.is_current_stream_capturing():
+        if targets_for is not None and not self.add_layout and not self._device_solver() \
+                and not torch.cuda.is_current_stream_capturing():
             pending = self._targets_begin(all_cls, all_box, list(targets_for[0]), list(targets_for[1]))
             if pending is not None:
                 pending['key'] = tuple(id(g) for g in targets_for[0])      # (the caller's box tensors: loss() checks them)
@@ -657,14 +665,22 @@ class VoxelFormerOccupancyHead(BaseModule):
         """Loss dict of the reference (head:1251-1384): last decoder layer -> ``loss_cls``,
         ``loss_bbox``, ``loss_occupancy``, ``loss_flow`` (zero); earlier layers -> ``d{i}.loss_*``.
         gt_bboxes_list: per sample [G, 7..9] boxes (gravity centre + dims + yaw [+ vel]);
-        gt_occupancy: int64 [bs, voxel_num] with ``occupancy_classes`` = empty."""
+        gt_occupancy: int64 [bs, voxel_num] with ``occupancy_classes`` = empty.
+        With the assigner's ``solver='device'``, ``gt_bboxes_list`` may be a ``PaddedGts`` (``pad_gts``; ``gt_labels_list``
+        is then unused): the static-shape form, with which nothing between the predictions and the loss dict touches the
+        host; the two lists are padded here otherwise."""
         all_cls, all_box = preds_dicts['all_cls_scores'], preds_dicts['all_bbox_preds']
         occ = preds_dicts['occupancy_preds']
         nl = len(all_cls)
         losses = {}
         pending = preds_dicts.get('pending_targets')
         padded = labels = None
-        if pending is not None and pending.get('key') == tuple(id(g) for g in gt_bboxes_list):
+        if isinstance(gt_bboxes_list, PaddedGts) or self._device_solver():
+            if not self._device_solver():
+                raise ValueError("loss: a PaddedGts needs train_cfg.assigner.solver = 'device'")
+            gts = gt_bboxes_list if isinstance(gt_bboxes_list, PaddedGts) else self.pad_gts(gt_bboxes_list, gt_labels_list)
+            targets = self._targets_device(all_cls, all_box, gts)
+        elif pending is not None and pending.get('key') == tuple(id(g) for g in gt_bboxes_list):
             targets = self._targets_finish(pending)         # started in forward(), solved under the occupancy head
         else:
             padded, labels = self._prepare_gts(gt_bboxes_list, gt_labels_list, all_box.device)
@@ -906,34 +922,9 @@ class VoxelFormerOccupancyHead(BaseModule):
         if gmax == 0:
             return None
         dev = all_box.device
-        gt_pad = all_box.new_zeros(bs, gmax, 9)
-        lab_pad = torch.zeros(bs, gmax, dtype=torch.long, device=dev)
-        widths = {int(g.shape[-1]) for g in gt_boxes}
-        if len(widths) == 1 and all(torch.is_tensor(g) and g.device == dev for g in gt_boxes) \
-                and all(torch.is_tensor(x) and x.device == dev for x in gt_labels):
-            # the usual case (every sample's boxes on the device, one width): the padded [bs, Gmax] tables are one
-            # concatenation and one indexed copy each, whatever the batch size (velocity columns stay zero, head:1316-1317)
-            width = min(widths.pop(), 9)
-            slots = self._gt_slots(tuple(counts), gmax, dev)
-            gt_pad.view(bs * gmax, 9)[:, :width].index_copy_(0, slots, torch.cat(list(gt_boxes))[:, :width].to(all_box.dtype))
-            lab_pad.view(-1).index_copy_(0, slots, torch.cat([x.reshape(-1) for x in gt_labels]).long())
-        else:
-            gt_boxes, gt_labels = self._prepare_gts(gt_boxes, gt_labels, dev)
-            for i, (g, lab) in enumerate(zip(gt_boxes, gt_labels)):
-                if counts[i]:
-                    gt_pad[i, :counts[i]] = g.to(all_box.dtype)
-                    lab_pad[i, :counts[i]] = lab.reshape(-1)
+        gt_pad, lab_pad = self._pad_tables(gt_boxes, gt_labels, counts, gmax, all_box.dtype, dev)
         with torch.no_grad():
-            c = a.cls_cost
-            p = all_cls.float().sigmoid()
-            neg = -(1 - p + c.eps).log() * (1 - c.alpha) * p.pow(c.gamma)
-            pos = -(p + c.eps).log() * c.alpha * (1 - p).pow(c.gamma)
-            cls_cost = ((pos - neg) * c.weight).gather(3, lab_pad[None, :, None, :].expand(nl, bs, nq, gmax))
-            gt_norm = normalize_bbox(gt_pad.view(-1, 9), a.pc_range).view(bs, gmax, -1)[..., :8]
-            # padded gts hold log(0): keep them finite, their columns are never handed to the solver
-            gt_norm = torch.nan_to_num(gt_norm, nan=0.0, posinf=0.0, neginf=0.0)
-            reg_cost = (all_box.float()[..., None, :8] - gt_norm[None, :, None]).abs().sum(-1) * a.reg_cost.weight
-            cost = cls_cost + reg_cost
+            cost = self._assignment_costs(all_cls, all_box, gt_pad, lab_pad)
             event = None
             if cost.is_cuda:
                 host = torch.empty(cost.shape, dtype=cost.dtype, pin_memory=True)
@@ -943,6 +934,57 @@ class VoxelFormerOccupancyHead(BaseModule):
             else:
                 host = cost
         return dict(host=host, event=event, counts=counts, gt_pad=gt_pad, lab_pad=lab_pad, shape=(nl, bs, nq, gmax))
+
+    def _pad_tables(self, gt_boxes, gt_labels, counts, gmax, dtype, dev):
+        """The per-sample gt lists as padded tables on ``dev``: boxes ``dtype`` [bs, gmax, 9] (velocity columns zero,
+        head:1316-1317) and labels int64 [bs, gmax]; rows past a sample's count stay zero."""
+        bs = len(counts)
+        gt_pad = torch.zeros(bs, gmax, 9, dtype=dtype, device=dev)
+        lab_pad = torch.zeros(bs, gmax, dtype=torch.long, device=dev)
+        widths = {int(g.shape[-1]) for g in gt_boxes}
+        if len(widths) == 1 and all(torch.is_tensor(g) and g.device == dev for g in gt_boxes) \
+                and all(torch.is_tensor(x) and x.device == dev for x in gt_labels):
+            # the usual case (every sample's boxes on the device, one width): the padded [bs, Gmax] tables are one
+            # concatenation and one indexed copy each, whatever the batch size (velocity columns stay zero, head:1316-1317)
+            width = min(widths.pop(), 9)
+            slots = self._gt_slots(tuple(counts), gmax, dev)
+            gt_pad.view(bs * gmax, 9)[:, :width].index_copy_(0, slots, torch.cat(list(gt_boxes))[:, :width].to(dtype))
+            lab_pad.view(-1).index_copy_(0, slots, torch.cat([x.reshape(-1) for x in gt_labels]).long())
+        else:
+            gt_boxes, gt_labels = self._prepare_gts(gt_boxes, gt_labels, dev)
+            for i, (g, lab) in enumerate(zip(gt_boxes, gt_labels)):
+                if counts[i]:
+                    gt_pad[i, :counts[i]] = g.to(dtype)
+                    lab_pad[i, :counts[i]] = lab.reshape(-1)
+        return gt_pad, lab_pad
+
+    def _assignment_costs(self, all_cls, all_box, gt_pad, lab_pad):
+        """Cost matrices fp32 [L, bs, Nq, Gmax] of every (layer, sample) against the padded gt tables: the formulas of
+        ``HungarianAssigner3D.assign`` (``FocalLossCost`` + ``BBox3DL1Cost`` on the normalised box).  Call under no_grad."""
+        a = self.assigner
+        nl, bs, nq, _ = all_cls.shape
+        gmax = gt_pad.shape[1]
+        c = a.cls_cost
+        p = all_cls.float().sigmoid()
+        neg = -(1 - p + c.eps).log() * (1 - c.alpha) * p.pow(c.gamma)
+        pos = -(p + c.eps).log() * c.alpha * (1 - p).pow(c.gamma)
+        cls_cost = ((pos - neg) * c.weight).gather(3, lab_pad[None, :, None, :].expand(nl, bs, nq, gmax))
+        gt_norm = normalize_bbox(gt_pad.view(-1, 9), a.pc_range).view(bs, gmax, -1)[..., :8]
+        # padded gts hold log(0): keep them finite, their columns are never handed to the solver
+        gt_norm = torch.nan_to_num(gt_norm, nan=0.0, posinf=0.0, neginf=0.0)
+        reg_cost = (all_box.float()[..., None, :8] - gt_norm[None, :, None]).abs().sum(-1) * a.reg_cost.weight
+        return cls_cost + reg_cost
+
+    def _targets_from_match(self, idx_t, gt_pad, lab_pad):
+        """Matched gt index per query, int64 [L, bs, Nq] (-1: background) -> (labels, bbox_targets, positive mask)."""
+        nl, bs, nq = idx_t.shape
+        gmax = gt_pad.shape[1]
+        pos_mask = idx_t >= 0
+        safe = idx_t.clamp(min=0)
+        labels = torch.where(pos_mask, lab_pad[None].expand(nl, bs, gmax).gather(2, safe),
+                             torch.full_like(safe, self.num_classes))
+        bbox_targets = gt_pad[None].expand(nl, bs, gmax, 9).gather(2, safe[..., None].expand(nl, bs, nq, 9))
+        return labels, bbox_targets, pos_mask
 
     def _targets_finish(self, ctx):
         """Second half: wait for the copy (only), solve the assignments on the host, build the targets on the device."""
@@ -964,12 +1006,83 @@ class VoxelFormerOccupancyHead(BaseModule):
                     idx[lvl, i, rows] = cols
         num_pos = (idx >= 0).reshape(nl, -1).sum(1).tolist()
         idx_t = _to_device_async(torch.from_numpy(idx), dev)
-        pos_mask = idx_t >= 0
-        safe = idx_t.clamp(min=0)
-        labels = torch.where(pos_mask, lab_pad[None].expand(nl, bs, gmax).gather(2, safe),
-                             torch.full_like(safe, self.num_classes))
-        bbox_targets = gt_pad[None].expand(nl, bs, gmax, 9).gather(2, safe[..., None].expand(nl, bs, nq, 9))
-        return labels, bbox_targets, pos_mask, num_pos
+        return self._targets_from_match(idx_t, gt_pad, lab_pad) + (num_pos,)
+
+    # ---- the same targets without the round trip (train_cfg.assigner.solver = 'device')
+    def _device_solver(self):
+        return getattr(self.assigner, 'solver', 'host') == 'device'
+
+    def pad_gts(self, gt_bboxes_list, gt_labels_list, capacity=None):
+        """The per-sample gt lists -> ``PaddedGts`` on the head's device, ``capacity`` boxes per sample (default: the
+        largest count): shapes that do not change with the counts, which a captured step needs -- new ground truth is
+        copied into the same three tensors."""
+        counts = [int(g.shape[0]) for g in gt_bboxes_list]
+        largest = max(counts) if counts else 0
+        cap = largest if capacity is None else int(capacity)
+        if largest > cap:
+            raise ValueError('pad_gts: a sample holds %d boxes, the capacity is %d' % (largest, cap))
+        dev = self.code_weights.device
+        boxes, labels = self._pad_tables(list(gt_bboxes_list), list(gt_labels_list), counts, cap, torch.float32, dev)
+        return PaddedGts(boxes, labels, _to_device_async(torch.tensor(counts, dtype=torch.int32), dev))
+
+    def _targets_device(self, all_cls, all_box, gts):
+        """``_batched_targets`` from a ``PaddedGts`` with the assignment solved where the costs are: the same cost matrices
+        [L, bs, Nq, cap], ``hipops.lsa_solve`` with every sample's count as its column bound (repeated per layer), the same
+        gathers.  Only launches are queued -- no copy to the host, no synchronisation, no host-built tensor -- so the call
+        can be captured.  -> (labels, bbox_targets, pos_mask, positives per layer as an int64 DEVICE tensor [L]).  A
+        problem scipy would raise on leaves its queries unmatched and is reported by a later call (``AssignmentFlag``).
+        CPU tensors: the same plumbing with scipy in place of the kernel."""
+        from .assigner import BBox3DL1Cost, FocalLossCost
+        a = self.assigner
+        if a is None or not isinstance(a.cls_cost, FocalLossCost) or not isinstance(a.reg_cost, BBox3DL1Cost):
+            raise NotImplementedError("solver='device' is built for FocalLossCost + BBox3DL1Cost assigners")
+        nl, bs, nq, _ = all_cls.shape
+        gt_pad, lab_pad, counts = gts.boxes.to(all_box.dtype), gts.labels, gts.counts
+        if gt_pad.shape[1] == 0:                             # no box anywhere: one padding column keeps the gathers well-formed
+            gt_pad, lab_pad = gt_pad.new_zeros(bs, 1, 9), lab_pad.new_zeros(bs, 1)
+        ncols = counts[None].expand(nl, bs)
+        with torch.no_grad():
+            if all_box.is_cuda:
+                from ..hipops import AssignmentFlag, lsa_solve
+                cost = self._assignment_costs(all_cls, all_box, gt_pad, lab_pad)
+                flag = AssignmentFlag.of(cost.device)
+                flag.poll()                                  # a problem of an EARLIER step is reported here
+                idx_t = lsa_solve(cost, ncols, bad=flag.dev).long()
+                flag.mirror(None)
+            else:
+                idx_t = self._solve_on_host(self._assignment_costs(all_cls, all_box, gt_pad, lab_pad), counts)
+        labels, bbox_targets, pos_mask = self._targets_from_match(idx_t, gt_pad, lab_pad)
+        # positives per layer, counted from the match like the host path: sum_b min(Nq, counts[b]) whenever every problem
+        # was solved, and still the number of rows with a target when a flagged problem left its queries unmatched
+        return labels, bbox_targets, pos_mask, pos_mask.sum((1, 2))
+
+    @staticmethod
+    def _solve_on_host(cost, counts):
+        """CPU stand-in of ``lsa_solve``: scipy on ``cost[l, b, :, :counts[b]]`` -> int64 [L, bs, Nq], -1 = unmatched."""
+        from .assigner import linear_sum_assignment
+        nl, bs, nq, _ = cost.shape
+        idx = torch.full((nl, bs, nq), -1, dtype=torch.long)
+        for lvl in range(nl):
+            for i, n in enumerate(counts.tolist()):
+                if n:
+                    rows, cols = linear_sum_assignment(cost[lvl, i, :, :n].numpy())
+                    idx[lvl, i, torch.from_numpy(rows)] = torch.from_numpy(cols)
+        return idx
+
+    def _device_normalisers(self, num_pos, per_layer):
+        """``_losses_from_targets``' two normalisers fp32 [2, L] from the positives per layer as a device tensor: formed in
+        fp64 and rounded to fp32 once, as the Python path does with its doubles (bit-identical on one rank).  With a process
+        group the rounded rows are divided by the world size and summed in fp32 -- ``reduce_mean``'s own arithmetic on the
+        Python path's ``new_tensor([value])``, so the two agree to the bit for any ``bg_cls_weight`` and world size -- in
+        ONE all-reduce for both rows, and stay on the device: no ``float(reduce_mean(...))`` round trip per decoder layer."""
+        import torch.distributed as dist
+        n = num_pos.to(torch.float64)
+        rows = torch.stack([n * 1.0 + (per_layer - n) * self.bg_cls_weight, n]).to(torch.float32)
+        if dist.is_available() and dist.is_initialized():
+            mean = rows / dist.get_world_size()
+            dist.all_reduce(mean, op=dist.ReduceOp.SUM)
+            rows = torch.stack([mean[0] if self.sync_cls_avg_factor else rows[0], mean[1]])
+        return rows.clamp(min=1.0)
 
     _GT_SLOTS = {}
 
@@ -993,14 +1106,17 @@ class VoxelFormerOccupancyHead(BaseModule):
         get weight 0 instead, so nothing here synchronises with the host."""
         nl = all_cls.shape[0]
         per_layer = pos_mask[0].numel()
-        cls_avg, pos_avg = [], []
-        for lvl in range(nl):
-            f = num_pos[lvl] * 1.0 + (per_layer - num_pos[lvl]) * self.bg_cls_weight
-            if self.sync_cls_avg_factor:
-                f = _mean_over_ranks(f, all_cls)
-            cls_avg.append(max(f, 1))
-            pos_avg.append(max(_mean_over_ranks(num_pos[lvl], all_cls), 1.0))
-        norm = _to_device_async(torch.tensor([cls_avg, pos_avg], dtype=torch.float32), all_cls.device)
+        if torch.is_tensor(num_pos):                     # (``_targets_device``: the counts never left the device)
+            norm = self._device_normalisers(num_pos, per_layer)
+        else:
+            cls_avg, pos_avg = [], []
+            for lvl in range(nl):
+                f = num_pos[lvl] * 1.0 + (per_layer - num_pos[lvl]) * self.bg_cls_weight
+                if self.sync_cls_avg_factor:
+                    f = _mean_over_ranks(f, all_cls)
+                cls_avg.append(max(f, 1))
+                pos_avg.append(max(_mean_over_ranks(num_pos[lvl], all_cls), 1.0))
+            norm = _to_device_async(torch.tensor([cls_avg, pos_avg], dtype=torch.float32), all_cls.device)
         cls_scores = all_cls.reshape(-1, self.cls_out_channels)
         elem = self.loss_cls(cls_scores, labels.reshape(-1), None, reduction_override='none')
         loss_cls = elem.reshape(nl, -1).sum(1) / norm[0]

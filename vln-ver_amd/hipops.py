@@ -15,7 +15,7 @@ from torch.autograd.function import once_differentiable
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # (VER_HIP_LIB: another build of the same ABI, e.g. the host-ASan build libver_hip_asan.so of tests/test_abi_cpu.py)
 LIB_PATH = os.environ.get('VER_HIP_LIB') or os.path.join(_PKG, 'libver_hip.so')
-ABI_VERSION = 30
+ABI_VERSION = 31
 HEADER = os.path.join(os.path.dirname(_PKG), 'include', 'ver_ops.h')
 _PARAMS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float}
 _RETURNS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'const char*': ctypes.c_char_p}
@@ -791,14 +791,28 @@ class LabelRangeFlag:
         elif self.event is None or not self.event.query():
             return
         if int(self.host[0]) != 0:
-            raise RuntimeError('FocalLoss: a target label outside [0, %s] reached the fused focal loss on %s (the loss of '
-                               'that call was NaN; F.one_hot raises on it in the reference)'
-                               % (self.classes, self.dev.device))
+            raise RuntimeError(self._message())
+
+    def _message(self):
+        return ('FocalLoss: a target label outside [0, %s] reached the fused focal loss on %s (the loss of that call was '
+                'NaN; F.one_hot raises on it in the reference)' % (self.classes, self.dev.device))
 
     def reset(self):
         self.dev.zero_()
         self.host.zero_()
         self.event = None
+
+
+class AssignmentFlag(LabelRangeFlag):
+    """The same sticky flag for ``lsa_solve``: a cost matrix with a NaN / -inf among its valid entries or without a finite
+    assignment (scipy raises on both in the reference's assigner) left its rows unmatched."""
+
+    _per_device = {}
+
+    def _message(self):
+        return ('HungarianAssigner3D: a cost matrix with a NaN / -inf entry or without a finite assignment reached lsa_solve '
+                'on %s (its queries were all left unmatched; scipy.optimize.linear_sum_assignment raises on it in the '
+                'reference)' % (self.dev.device,))
 
 
 class SigmoidFocalLossSumFunction(Function):
@@ -1244,6 +1258,40 @@ def occ_confusion(logits, labels, thresholds=(0.25,), samples=1, hist=None):
     _launch('ver_occ_confusion', lambda: lib().ver_occ_confusion(
         _p(logits), dt, n // samples, samples, c, _p(labels), host_thr, len(thr), _p(hist), _stream()))
     return hist
+
+
+# ------------------------------------------------------------------------------------------
+LSA_MAX = 1024            # ver_lsa_solve: rows and column capacity of a problem
+
+
+def lsa_solve(cost, ncols, match=None, bad=None):
+    """Batched rectangular linear sum assignment (ver_lsa_solve; ``scipy.optimize.linear_sum_assignment`` on
+    ``cost[p, :, :ncols[p]]`` for every problem p): cost fp32 [..., R, Ccap], ncols int32 with one entry per problem ->
+    int32 match [..., R], the column assigned to each row or -1.  ``match``: a contiguous int32 buffer of that shape to
+    write into; ``bad``: an int32 device scalar that gets 1 ORed in when a problem could not be solved (NaN / -inf, no
+    finite assignment; never cleared here).  One launch, no allocation besides ``match``, no host synchronisation."""
+    cost = _gpu(cost, 'cost', torch.float32)
+    if cost.dim() < 2:
+        raise ValueError('lsa_solve: cost must be [..., R, Ccap]')
+    r, ccap = cost.shape[-2:]
+    lead = tuple(cost.shape[:-2])
+    n = 1
+    for d in lead:
+        n *= d
+    ncols = _gpu(ncols, 'ncols', torch.int32).reshape(-1)
+    if ncols.numel() != n:
+        raise ValueError('lsa_solve: %d column counts for %d problems' % (ncols.numel(), n))
+    if match is None:
+        match = torch.empty(lead + (r,), dtype=torch.int32, device=cost.device)
+    elif (tuple(match.shape) != lead + (r,) or match.dtype != torch.int32 or not match.is_contiguous()
+          or match.device != cost.device):
+        raise ValueError('lsa_solve: match must be a contiguous int32 %s tensor on %s' % (lead + (r,), cost.device))
+    if bad is not None and (bad.numel() != 1 or bad.dtype != torch.int32 or bad.device != cost.device):
+        raise ValueError('lsa_solve: bad must be one int32 on %s' % (cost.device,))
+    if r == 0:
+        return match
+    _launch('ver_lsa_solve', lambda: lib().ver_lsa_solve(_p(cost), _p(ncols), _p(match), _p(bad), n, r, ccap, _stream()))
+    return match
 
 
 # ------------------------------------------------------------------------------------------
