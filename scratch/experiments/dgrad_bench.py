@@ -50,8 +50,8 @@ if 'check' in what:
             'OK' if err < 4e-3 else 'FAIL'), flush=True)
 
 if 'big' in what:
-    # layer 3 / 2 (N = 1536, kt = 14464): class ranges of dense_heads/upsample.py::_layer_plan_z4 for ci = 768
-    up = importlib.import_module('vln-ver_amd.dense_heads.upsample')
+    # layer 3 / 2 (N = 1536, kt = 14464): class ranges of dense_heads/lattice_plan.py::_layer_plan_z4 for ci = 768
+    up = importlib.import_module('vln-ver_amd.dense_heads.lattice_plan')
     plan, kt, total_rows, taps, offs = up._layer_plan_z4(768, torch.device(dev))
     rng = [(plan[c][0], plan[c][1] - plan[c][0]) for c in up._CLASSES]
     print('class ranges', rng, 'kt', kt)

@@ -1,8 +1,8 @@
-"""The lattice algebra of ``upsample.py`` / ``occ_proj_lattice.py`` as plain torch ops on any device and dtype: what the CPU
-suite checks in fp64 against ``conv_transpose3d`` (tests/test_head_cpu.py, test_modules_cpu.py).  The product path never
-comes here with a GPU tensor of a dtype the HIP kernels take: ``upsample._algebra(tensor)`` is the ONE place that chooses
-between this module and the HIP kernels (by the tensor's device, never by "extension missing" -- without libver_hip.so a GPU
-tensor raises)."""
+"""The lattice algebra of ``upsample.py`` / ``occ_proj_lattice.py`` (index geometry: ``lattice_plan.py``) as plain torch ops on
+any device and dtype: what the CPU suite checks in fp64 against ``conv_transpose3d`` (tests/test_head_cpu.py,
+test_modules_cpu.py).  The product path never comes here with a GPU tensor of a dtype the HIP kernels take:
+``upsample._algebra(tensor)`` is the ONE place that chooses between this module and the HIP kernels (by the tensor's device,
+never by "extension missing" -- without libver_hip.so a GPU tensor raises)."""
 import torch
 import torch.nn.functional as F
 
