@@ -616,6 +616,54 @@ int ver_clip_adamw_step_tensors(void* const* table, const long* sizes, const int
 int ver_lsa_solve(const float* cost, const int32_t* ncols, int32_t* match, int32_t* bad,
                   int P, int R, int Ccap, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Detection mAP / mAR on the device (additive to ABI 31): rotated 3-D box IoU and the per-image matching of the indoor
+ * protocol the reference evaluates detections with (MP3DDataset.evaluate, mp3docc_dataset.py:304-384, calling
+ * datasets/indoor_eval.py:196 with iou_thr = (0.10, 0.25, 0.5, 0.75)).
+ * Box format everywhere: f32 [.., 7] = (x, y, z_bottom, dx, dy, dz, yaw) -- what the head's _to_box_type produces and
+ * LiDARInstance3DBoxes(..., origin=(0.5, 0.5, 0)) holds (box_type_3d = 'LiDAR', vocc.py:238).
+ *
+ * ver_box3d_overlaps: mmdet3d's BaseInstance3DBoxes.overlaps(mode='iou') as indoor_eval.py:102 calls it
+ * (`pred_cur.overlaps(pred_cur, gt_cur)`: height overlap times the rotated BEV intersection), batched.
+ *   a    f32 [S, Acap, 7]          b    f32 [S, Bcap, 7]
+ *   na   i32 device [S] or NULL    nb   i32 device [S] or NULL   valid boxes of sample s; NULL: every slot is valid;
+ *                                                                counts outside [0, cap] are clamped
+ *   iou  f32 [S, Acap, Bcap], written in full; slots beyond the counts get 0
+ *     h   = max(0, min(za + dza, zb + dzb) - max(za, zb))
+ *     bev = area of the intersection of the rotated rectangles (x, y, dx, dy, yaw)
+ *     o   = bev * h,    iou = o / max(dxa dya dza + dxb dyb dzb - o, 1e-8)
+ * OUR DEFINITION where the reference's behaviour is undefined: a box with a non-finite entry or a dimension <= 0 overlaps
+ * nothing -- IoU 0, never NaN (so does a pair whose volumes leave the fp32 range).
+ * One launch, no memset node, no allocation, no host read.  S, Acap or Bcap == 0 launches nothing.
+ */
+int ver_box3d_overlaps(const float* a, const int32_t* na, const float* b, const int32_t* nb, float* iou,
+                       int S, int Acap, int Bcap, void* stream);
+
+/* ver_det_match: the per-image half of eval_det_cls (indoor_eval.py:54-143) for a batch in one launch.
+ *   pred_boxes f32 [S, Pcap, 7], pred_labels i32 [S, Pcap], pred_scores f32 [S, Pcap], pred_valid u8 [S, Pcap]
+ *   gt_boxes   f32 [S, Gcap, 7], gt_labels   i32 [S, Gcap], ngt i32 device [S] (clamped to [0, Gcap])
+ *   thresholds HOST f32 [num_thresholds], 1 <= num_thresholds <= 8 (copied into the kernel arguments, as ver_occ_confusion)
+ *   iou_max f32, gt_index i32, tp_bits u8: [S, Pcap], written in full
+ *   npos    i64 [num_classes], ACCUMULATED and never cleared: npos[c] += valid ground truths of class c in the batch
+ * For a valid prediction d of sample s with label c: gt_index = the ground truth of class c of the same sample with the
+ * largest IoU (the first of equal maxima, the reference's `iou > iou_max`; a NaN never wins), iou_max = that IoU; without a
+ * candidate gt_index = -1 and iou_max = 0.  Bit t of tp_bits is set iff iou_max > thresholds[t] (strict, as in the
+ * reference) and no other valid prediction d' of the sample has the same gt_index, iou_max[d'] > thresholds[t] and goes
+ * before d in the evaluation order: score descending, then slot ascending.  That is the reference's sequential "mark the
+ * ground truth as detected" loop -- a later prediction whose best ground truth is taken is a false positive, it does not
+ * fall back to its second best; the loop's `det` flags are per image and the global score order restricted to an image is
+ * that image's score order, so the flags are resolved per sample, in parallel.
+ * Predictions with pred_valid == 0 or a label outside [0, num_classes) match nothing (gt_index -1, tp_bits 0); ground
+ * truths with a label outside the range are neither counted nor matched.  Only same-class pairs are clipped.
+ * One workgroup per sample (csrc/ver_boxiou.hip).  Supported: 1 <= Pcap <= 1024, 0 <= Gcap <= 1024, Pcap * Gcap <= 16 384
+ * (VER_EUNSUPPORTED beyond); S == 0 launches nothing; Gcap == 0 or ngt[s] == 0: every valid prediction is a false positive.
+ * One launch, no memset node, no allocation, no host read.
+ */
+int ver_det_match(const float* pred_boxes, const int32_t* pred_labels, const float* pred_scores,
+                  const uint8_t* pred_valid, const float* gt_boxes, const int32_t* gt_labels, const int32_t* ngt,
+                  const float* thresholds, int num_thresholds, float* iou_max, int32_t* gt_index,
+                  uint8_t* tp_bits, int64_t* npos, int num_classes, int S, int Pcap, int Gcap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

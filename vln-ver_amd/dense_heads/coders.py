@@ -66,7 +66,30 @@ class _TopKCoder:
 
 @BBOX_CODERS.register_module(force=True)
 class NMSFreeCoder(_TopKCoder):
-    pass
+
+    def decode_padded(self, preds_dicts):
+        """The batched, fixed-shape twin of ``decode``: one ``topk`` over [bs, Nq * C] of the last decoder layer ->
+        (boxes [bs, K, box_dim], scores [bs, K], labels int64 [bs, K], valid uint8 [bs, K]), K = min(max_num, Nq * C).
+        ``valid``: the centre lies inside ``post_center_range`` and the score is above ``score_threshold`` -- the slots
+        ``decode`` keeps, with the same values in the same order.  No boolean indexing, no host synchronisation."""
+        cls_scores = preds_dicts['all_cls_scores'][-1].sigmoid()
+        bbox_preds = preds_dicts['all_bbox_preds'][-1]
+        bs, nq, nc = cls_scores.shape
+        scores, indexs = cls_scores.reshape(bs, nq * nc).topk(min(self.max_num, nq * nc), dim=1)
+        labels = indexs % self.num_classes
+        bbox_index = indexs // self.num_classes
+        picked = bbox_preds.gather(1, bbox_index[..., None].expand(-1, -1, bbox_preds.shape[-1]))
+        boxes = denormalize_bbox(picked.reshape(-1, picked.shape[-1]), self.pc_range).reshape(bs, picked.shape[1], -1)
+        if self.post_center_range is None:
+            raise NotImplementedError('Need to reorganize output as a batch, only '
+                                      'support post_center_range is not None for now!')
+        rng = [float(v) for v in self.post_center_range]       # compared as scalars: no host-built tensor to copy over
+        valid = torch.ones_like(scores, dtype=torch.bool)
+        for axis in range(3):
+            valid = valid & (boxes[..., axis] >= rng[axis]) & (boxes[..., axis] <= rng[3 + axis])
+        if self.score_threshold is not None:
+            valid &= scores > self.score_threshold
+        return boxes, scores, labels, valid.to(torch.uint8)
 
 
 @BBOX_CODERS.register_module(force=True)

@@ -893,6 +893,15 @@ class VoxelFormerOccupancyHead(BaseModule):
         metas = img_metas or [None] * len(preds)
         return [[self._to_box_type(p['bboxes'], m), p['scores'], p['labels']] for p, m in zip(preds, metas)]
 
+    def get_bboxes_padded(self, preds_dicts):
+        """``get_bboxes`` in fixed shapes (``bbox_coder.decode_padded``): (boxes [bs, K, box_dim] with bottom-centre z as
+        ``_to_box_type`` makes it, scores [bs, K], labels [bs, K], valid uint8 [bs, K]); the slots with ``valid`` set are
+        ``get_bboxes``' boxes in the same order.  Launches only -- what ``DeviceDetMetrics.add`` feeds to the matcher."""
+        boxes, scores, labels, valid = self.bbox_coder.decode_padded(preds_dicts)
+        boxes = boxes.clone()
+        boxes[..., 2] = boxes[..., 2] - boxes[..., 5] * 0.5
+        return boxes, scores, labels, valid
+
     def get_layouts(self, preds_dicts, img_metas=None):
         """head:1478-1502: layout boxes of the last decoder layer inside the layout range."""
         preds = self.layout_coder.decode(preds_dicts)

@@ -1295,6 +1295,87 @@ def lsa_solve(cost, ncols, match=None, bad=None):
 
 
 # ------------------------------------------------------------------------------------------
+DET_MATCH_MAX_BOXES = 1024      # ver_det_match: Pcap, Gcap
+DET_MATCH_MAX_PAIRS = 16384     # ver_det_match: Pcap * Gcap
+DET_MATCH_MAX_THRESHOLDS = 8
+
+
+def _boxes7(t, name, what):
+    t = _gpu(t, name, torch.float32)
+    if t.dim() != 3 or t.shape[-1] != 7:
+        raise ValueError('%s: %s must be [S, N, 7] = (x, y, z_bottom, dx, dy, dz, yaw), got %s' % (what, name, tuple(t.shape)))
+    return t
+
+
+def _counts(t, name, what, s, device):
+    if t is None:
+        return None
+    t = _gpu(t, name, torch.int32).reshape(-1)
+    if t.numel() != s or t.device != device:
+        raise ValueError('%s: %s must hold one int32 per sample (%d) on %s' % (what, name, s, device))
+    return t
+
+
+def box3d_overlaps(a, b, na=None, nb=None):
+    """Rotated 3-D box IoU (ver_box3d_overlaps; mmdet3d ``overlaps(mode='iou')`` as the reference's indoor_eval.py:102 calls
+    it, batched): a fp32 [S, A, 7], b fp32 [S, B, 7] bottom-centre boxes (x, y, z, dx, dy, dz, yaw); na / nb: int32 [S]
+    valid boxes per sample (None: all) -> fp32 [S, A, B], 0 for slots beyond the counts and for boxes with a non-finite
+    entry or a dimension <= 0.  One launch, no host synchronisation."""
+    a, b = _boxes7(a, 'a', 'box3d_overlaps'), _boxes7(b, 'b', 'box3d_overlaps')
+    if a.shape[0] != b.shape[0] or a.device != b.device:
+        raise ValueError('box3d_overlaps: a %s and b %s must share the sample axis and the device' % (tuple(a.shape), tuple(b.shape)))
+    s, ca, cb = a.shape[0], a.shape[1], b.shape[1]
+    na, nb = _counts(na, 'na', 'box3d_overlaps', s, a.device), _counts(nb, 'nb', 'box3d_overlaps', s, a.device)
+    iou = torch.empty(s, ca, cb, dtype=torch.float32, device=a.device)
+    if iou.numel():
+        _launch('ver_box3d_overlaps', lambda: lib().ver_box3d_overlaps(_p(a), _p(na), _p(b), _p(nb), _p(iou), s, ca, cb, _stream()))
+    return iou
+
+
+def det_match(pred_boxes, pred_labels, pred_scores, pred_valid, gt_boxes, gt_labels, ngt, thresholds, npos):
+    """Per-image matching of the indoor detection protocol (ver_det_match; the reference's eval_det_cls,
+    indoor_eval.py:54-143): pred_boxes fp32 [S, P, 7], pred_labels int32 [S, P], pred_scores fp32 [S, P], pred_valid uint8
+    [S, P]; gt_boxes fp32 [S, G, 7], gt_labels int32 [S, G], ngt int32 [S]; ``thresholds``: 1..8 IoU thresholds;
+    ``npos``: a contiguous int64 [num_classes] tensor that the valid ground truths per class are ADDED to.
+    -> (iou_max fp32, gt_index int32, tp_bits uint8), each [S, P]: the best same-class ground truth of every valid
+    prediction and, per threshold bit, whether it is the first in (score descending, slot ascending) order to claim it.
+    One launch, no host synchronisation."""
+    what = 'det_match'
+    pred_boxes, gt_boxes = _boxes7(pred_boxes, 'pred_boxes', what), _boxes7(gt_boxes, 'gt_boxes', what)
+    s, p = pred_boxes.shape[:2]
+    g = gt_boxes.shape[1]
+    dev = pred_boxes.device
+    pred_labels = _gpu(pred_labels, 'pred_labels', torch.int32)
+    pred_scores = _gpu(pred_scores, 'pred_scores', torch.float32)
+    pred_valid = _gpu(pred_valid, 'pred_valid', torch.uint8)
+    gt_labels = _gpu(gt_labels, 'gt_labels', torch.int32)
+    for name, t, shape in (('pred_labels', pred_labels, (s, p)), ('pred_scores', pred_scores, (s, p)),
+                           ('pred_valid', pred_valid, (s, p)), ('gt_boxes', gt_boxes, (s, g, 7)), ('gt_labels', gt_labels, (s, g))):
+        if tuple(t.shape) != shape or t.device != dev:
+            raise ValueError('%s: %s must be %s on %s, got %s on %s' % (what, name, shape, dev, tuple(t.shape), t.device))
+    ngt = _counts(ngt, 'ngt', what, s, dev)
+    if ngt is None:
+        raise ValueError('det_match: ngt is required')
+    thr = [float(t) for t in thresholds]
+    if not 1 <= len(thr) <= DET_MATCH_MAX_THRESHOLDS:
+        raise ValueError('det_match: %d thresholds (1..%d)' % (len(thr), DET_MATCH_MAX_THRESHOLDS))
+    if npos.dim() != 1 or npos.dtype != torch.int64 or not npos.is_contiguous() or npos.device != dev or npos.numel() < 1:
+        raise ValueError('det_match: npos must be a contiguous int64 [num_classes] tensor on %s' % (dev,))
+    if p < 1 or p > DET_MATCH_MAX_BOXES or g > DET_MATCH_MAX_BOXES or p * g > DET_MATCH_MAX_PAIRS:
+        raise ValueError('det_match: P=%d G=%d (1 <= P <= %d, G <= %d, P * G <= %d)'
+                         % (p, g, DET_MATCH_MAX_BOXES, DET_MATCH_MAX_BOXES, DET_MATCH_MAX_PAIRS))
+    iou_max = torch.empty(s, p, dtype=torch.float32, device=dev)
+    gt_index = torch.empty(s, p, dtype=torch.int32, device=dev)
+    tp_bits = torch.empty(s, p, dtype=torch.uint8, device=dev)
+    if s:
+        host_thr = (ctypes.c_float * len(thr))(*thr)
+        _launch('ver_det_match', lambda: lib().ver_det_match(
+            _p(pred_boxes), _p(pred_labels), _p(pred_scores), _p(pred_valid), _p(gt_boxes), _p(gt_labels), _p(ngt), host_thr,
+            len(thr), _p(iou_max), _p(gt_index), _p(tp_bits), _p(npos), npos.numel(), s, p, g, _stream()))
+    return iou_max, gt_index, tp_bits
+
+
+# ------------------------------------------------------------------------------------------
 def wgrad_tn_supported(a, g):
     """Shapes / strides ``wgrad_tn`` takes: bf16 GPU matrices, unit column stride, 16-byte aligned rows."""
     return (a.is_cuda and g.is_cuda and a.dtype == torch.bfloat16 and g.dtype == torch.bfloat16 and a.dim() == 2
