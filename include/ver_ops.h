@@ -492,6 +492,27 @@ int  ver_occ_confusion(const void* logits, int dtype, long rows_per_sample, int 
                        const float* thresholds, int num_thresholds, int64_t* hist, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The same two results WITHOUT the logits: the classification runs in the epilogue of the fused MLP forward kernel
+ * (csrc/ver_occ_mlp.hip), on the bf16 logits ver_occ_mlp_forward would have stored -- they never reach memory.
+ *   x, image, vectors, width, classes, eps, flags: as ver_occ_mlp_forward (flags bit 0 = first_linear, bit 1 =
+ *               VER_OCC_MLP_CENTERED; x and image 16-byte aligned; another width / class count: VER_EUNSUPPORTED)
+ * ver_occ_mlp_confusion: labels, rows_per_sample, samples, thresholds (HOST array, copied into the kernel arguments: a
+ *   captured launch keeps them), num_thresholds (1 to 8) and hist (8-byte aligned, ACCUMULATED, never cleared) as
+ *   ver_occ_confusion; sample s owns rows [s, s + 1) * rows_per_sample of x.  CONTRACT: it adds to hist exactly what
+ *   ver_occ_mlp_forward followed by ver_occ_confusion on its bf16 logits adds.  rows_per_sample == 0 or samples == 0:
+ *   nothing is launched, no pointer is looked at, hist is unchanged.
+ * ver_occ_mlp_classes: cls u8 [N] = threshold_class(row_argmax(logits of the row), threshold): the class
+ *   ver_occ_predict pairs with the row, `classes` (16) for an empty row; prob f32 [N] or NULL = the probability of the best
+ *   class (row_argmax's pb, bit for bit).  N == 0: nothing is launched.
+ * One launch each, no memset node, no allocation, no host read.
+ */
+int ver_occ_mlp_confusion(const void* x, const void* image, const float* vectors, const uint8_t* labels,
+                          long rows_per_sample, int samples, const float* thresholds, int num_thresholds,
+                          int64_t* hist, int width, int classes, float eps, int flags, void* stream);
+int ver_occ_mlp_classes(const void* x, const void* image, const float* vectors, uint8_t* cls, float* prob,
+                        long N, float threshold, int width, int classes, float eps, int flags, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Weight gradient of the head's GEMM layers with ROWS on the contraction axis (ABI 24):
  *     out[Ka, N] = A[M, Ka]^T G[M, N]
  * A = the operand of the forward GEMM (tap matrix of a lattice layer / gathered occ_proj rows), G = the gradient of

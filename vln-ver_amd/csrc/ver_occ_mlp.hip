@@ -24,6 +24,7 @@
 // Weight fragments live in LDS in fragment order (one conflict-free ds_read_b128 per fragment),
 // built once per step by `ver_occ_mlp_pack` from the fp32 parameters.
 #include <cstdlib>
+#include "ver_classify.h"
 #include "ver_common.h"
 
 namespace {
@@ -248,20 +249,107 @@ __device__ __forceinline__ void ln_relu_nat(bf16x8 (&x)[4], const float* gam, co
 }
 }  // namespace
 
+// (best class, its probability) of row c of one layer-3 tile, in all four lanes that share the row: lane (c, g) enters with
+// the fp32 logits of classes 4g..4g+3.  The logits are rounded to bf16 exactly as the stored ones are (pack4) and widened
+// back, so the classification is that of the logits ver_occ_mlp_forward writes.
+__device__ __forceinline__ void classify_tile(f32x4 acc, int lane, int& best, float& pb) {
+    typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+    const u32x2_t w = __builtin_bit_cast(u32x2_t, pack4(acc));
+    const float xv[4] = {__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16),
+                         __uint_as_float(w.y & 0xffff0000u)};
+    int b = 4 * (lane >> 4);
+    float p = ver_class_prob(xv[0]);
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+        const float pj = ver_class_prob(xv[j]);
+        if (ver_class_takes(pj, p)) {
+            b = 4 * (lane >> 4) + j;
+            p = pj;
+        }
+    }
+#pragma unroll
+    for (int mask = 16; mask <= 32; mask <<= 1) {
+        const int ob = __shfl_xor(b, mask, 64);
+        const float op = __shfl_xor(p, mask, 64);
+        const bool upper = lane & mask;                 // this lane holds the higher classes of the pair: the partner is A
+        ver_class_merge(upper ? ob : b, upper ? op : p, upper ? b : ob, upper ? p : op, b, p);
+    }
+    best = b;
+    pb = p;
+}
+
+// Epilogues of the forward kernel (template parameter EPI).  kEpiLogits is the kernel as ver_occ_mlp_forward launches it; the
+// other two end in the classification of ver_classify.h on the bf16 logits that kernel would have stored, and store none:
+//   kEpiConfusion (ver_occ_mlp_confusion): the (label, prediction) pairs of T thresholds counted into hist[sample];
+//   kEpiClasses   (ver_occ_mlp_classes):   one class byte (and optionally the best probability) per row.
+// After layer 3 lane (c, g) holds classes 4g..4g+3 of row 16 rt + c: an in-lane arg-max, two cross-lane merges (xor 16, xor 32;
+// the partner with the lower g holds the lower classes) and all four lanes of a row hold its (best, pb); lane (c, g) then keeps
+// the row of tile rt = g, i.e. row r0 + lane of the wave's 64-row block -- one row per lane, labels and class bytes coalesced.
+// Confusion mode deals the rows PER SAMPLE: workgroup (bx, s) owns rows [bx, bx + 1) * kEpiChunkRows of sample s and nothing
+// else, so no block straddles two samples and the histogram is flushed once, at the end.  A workgroup counts at most
+// kEpiChunkRows < 2^16 rows: its bins are 16 bits wide, two to an LDS word (a 32-bit add of 1 << 16 * (bin & 1) cannot
+// carry), [8, 17, 17] bins in 4 624 B instead of 9 248 -- with all 68 fragments (first_linear = 1) that is 77 392 B per
+// workgroup and two workgroups still share a CU's 160 KB.  With first_linear = 0 section kF2 is never read: those
+// instantiations stage 36 fragments (layer 3 moves up to fragment 32), 44 624 B.
+constexpr int kEpiLogits = 0, kEpiConfusion = 1, kEpiClasses = 2;
+constexpr int kEpiMaxT = 8;
+constexpr int kEpiK = kC + 1;
+constexpr int kEpiBinWords = (kEpiMaxT * kEpiK * kEpiK + 1) / 2;
+constexpr long kEpiChunkRows = 8192;                    // rows of one workgroup in confusion mode: 32 slabs of 4 waves x 64 rows
+static_assert(kEpiChunkRows < 65536 && kEpiChunkRows % 256 == 0, "16-bit bins hold a workgroup's whole count");
+
+template <int EPI>
+struct FwdEpilogue {};
+template <>
+struct FwdEpilogue<kEpiConfusion> {
+    const uint8_t* labels;
+    unsigned long long* hist;          // [samples, T, 17, 17]
+    float thr[kEpiMaxT];
+    int T;
+};
+template <>
+struct FwdEpilogue<kEpiClasses> {
+    uint8_t* cls;
+    float* prob;                       // may be null
+    float thr;
+};
+
 // L1 = false (first_linear = 0, ver_ops.h): x is the output of the first Linear already.  The chain starts with the first
 // LayerNorm in the natural fragment layout; the image was packed with W2 in W1's place, so section kF1 holds W2 with the
 // natural k order that layout needs (and kB1, in the backward kernel, W2's dgrad with natural-order output rows).
 // CENTERED (flags bit 1): every LayerNorm input has zero row mean by construction (see ln_relu_tile).
 // STATS: also write 1/std of both LayerNorms per row (rstd f32 [N, 2]; 32-bit buffer addressing: N < 2^28 rows).
-template <int RT, bool L1, bool CENTERED = false, bool STATS = false>
+template <int RT, bool L1, bool CENTERED = false, bool STATS = false, int EPI = kEpiLogits>
 __global__ __launch_bounds__(256, 2) void k_occ_mlp_fwd(const __bf16* __restrict__ x, const __bf16* __restrict__ img,
                                                         const float* __restrict__ vec, __bf16* __restrict__ logits,
-                                                        long N, float eps, float* __restrict__ rstd) {
+                                                        long N, float eps, float* __restrict__ rstd, FwdEpilogue<EPI> ep) {
+    static_assert(EPI == kEpiLogits || (RT == 4 && !STATS), "the classifying epilogues keep one row per lane: 64-row blocks");
+    // the classifying instantiations of the folded chain stage only the sections it reads: kF1 and kF3
+    constexpr bool kCompact = EPI != kEpiLogits && !L1;
+    constexpr int kStaged = kCompact ? kF2 + (kFwdFrags - kF3) : kFwdFrags, kL3 = kCompact ? kF2 : kF3;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    bf16x8* frag = reinterpret_cast<bf16x8*>(smem);                       // [kFwdFrags][64]
-    float* sv = reinterpret_cast<float*>(smem + kFwdFrags * 1024);        // vectors
-    for (int i = threadIdx.x; i < kFwdFrags * 64; i += 256) frag[i] = reinterpret_cast<const bf16x8*>(img)[i];
+    bf16x8* frag = reinterpret_cast<bf16x8*>(smem);                       // [kStaged][64]
+    float* sv = reinterpret_cast<float*>(smem + kStaged * 1024);          // vectors
+    if constexpr (kCompact) {
+        for (int i = threadIdx.x; i < kStaged * 64; i += 256)
+            frag[i] = reinterpret_cast<const bf16x8*>(img)[i < kF2 * 64 ? i : i + (kF3 - kF2) * 64];
+    } else {
+        for (int i = threadIdx.x; i < kFwdFrags * 64; i += 256) frag[i] = reinterpret_cast<const bf16x8*>(img)[i];
+    }
     for (int i = threadIdx.x; i < kVecFloats; i += 256) sv[i] = vec[i];
+    [[maybe_unused]] unsigned* bins = reinterpret_cast<unsigned*>(sv + kVecFloats);        // confusion mode: [T, 17, 17] 16-bit bins, two per word
+    [[maybe_unused]] int empty_empty[kEpiMaxT];                                            // the dominant bin, counted per lane
+    if constexpr (EPI == kEpiConfusion) {
+        for (int i = threadIdx.x; i < kEpiBinWords; i += 256) bins[i] = 0;
+#pragma unroll
+        for (int t = 0; t < kEpiMaxT; ++t) empty_empty[t] = 0;
+        // this workgroup's rows of its sample (N = rows per sample on entry): from here on x / labels / N are the chunk's
+        const long first = (long)blockIdx.x * kEpiChunkRows;
+        const long base = (long)blockIdx.y * N + first;
+        x += base * kW;
+        ep.labels += base;
+        N = N - first < kEpiChunkRows ? N - first : kEpiChunkRows;
+    }
     __syncthreads();
     // (wave index as a SCALAR: the per-block buffer resource below is built from it; as a vector value every load through the
     //  resource becomes a readfirstlane loop)
@@ -270,7 +358,9 @@ __global__ __launch_bounds__(256, 2) void k_occ_mlp_fwd(const __bf16* __restrict
     const long nblk = (N + 16 * RT - 1) / (16 * RT);
     // (stores beyond row N - 1, and those of the lanes g != 0 -- sent there on purpose -- fall outside the range and are dropped)
     const __amdgpu_buffer_rsrc_t rs_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)rstd, 0, STATS ? (int)(N * 8) : 0, 0x00020000);
-    for (long blk = (long)blockIdx.x * 4 + wave; blk < nblk; blk += (long)gridDim.x * 4) {
+    // (confusion mode: the four waves share the workgroup's own chunk; grid-stride otherwise)
+    for (long blk = EPI == kEpiConfusion ? (long)wave : (long)blockIdx.x * 4 + wave; blk < nblk;
+         blk += EPI == kEpiConfusion ? 4 : (long)gridDim.x * 4) {
         const long r0 = blk * (16 * RT);
         // the weight fragments are loop invariant: hide that from LICM, which would otherwise hoist
         // all 68 of them (272 VGPRs) out of the row loop
@@ -279,6 +369,10 @@ __global__ __launch_bounds__(256, 2) void k_occ_mlp_fwd(const __bf16* __restrict
         const bf16x8* fr = frag + lane_off;
         const float* sv_g = sv + 4 * (lane_off >> 4);
         bf16x8 bf[RT][4];
+        int label = 255;                                // (requested before the chain, used after it)
+        if constexpr (EPI == kEpiConfusion) {
+            if (r0 + lane < N) label = ep.labels[r0 + lane];
+        }
         {
             // the block's rows through ONE buffer resource (base = its first row, size = its rows below N): sixteen
             // unconditional loads issued back to back, rows past N read as zeros.  (As `r < N ? load : 0` every load sat in its
@@ -337,14 +431,63 @@ __global__ __launch_bounds__(256, 2) void k_occ_mlp_fwd(const __bf16* __restrict
         for (int rt = 0; rt < RT; ++rt) lo[rt] = b3;
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
-            const bf16x8 a = fr[(kF3 + kt) * 64];
+            const bf16x8 a = fr[(kL3 + kt) * 64];
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) lo[rt] = mfma(a, bf[rt][kt], lo[rt]);
         }
+        if constexpr (EPI == kEpiLogits) {
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-            const long r = r0 + rt * 16 + c;
-            if (r < N) *reinterpret_cast<bf16x4*>(logits + r * kC + 4 * g) = pack4(lo[rt]);
+            for (int rt = 0; rt < RT; ++rt) {
+                const long r = r0 + rt * 16 + c;
+                if (r < N) *reinterpret_cast<bf16x4*>(logits + r * kC + 4 * g) = pack4(lo[rt]);
+            }
+        } else {
+            int best = 0;
+            float pbest = 0.0f;
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                int b;
+                float p;
+                classify_tile(lo[rt], lane, b, p);
+                if (rt == g) {                           // lane (c, g) keeps row 16 g + c of the block: row r0 + lane
+                    best = b;
+                    pbest = p;
+                }
+            }
+            if constexpr (EPI == kEpiClasses) {
+                const long r = r0 + lane;
+                if (r < N) {
+                    ep.cls[r] = (uint8_t)threshold_class(best, pbest, ep.thr, kC);
+                    if (ep.prob) ep.prob[r] = pbest;
+                }
+            } else if (label < kEpiK) {                  // the reference's `gt < n_cl`; rows past the chunk carry 255
+#pragma unroll
+                for (int t = 0; t < kEpiMaxT; ++t) {
+                    if (t >= ep.T) break;
+                    const int pred = threshold_class(best, pbest, ep.thr[t], kC);
+                    const int bin = (t * kEpiK + label) * kEpiK + pred;
+                    if (label == kC && pred == kC) ++empty_empty[t];
+                    else atomicAdd(&bins[bin >> 1], 1u << (16 * (bin & 1)));
+                }
+            }
+        }
+    }
+    if constexpr (EPI == kEpiConfusion) {
+#pragma unroll
+        for (int t = 0; t < kEpiMaxT; ++t) {
+            if (t >= ep.T) break;
+            int v = empty_empty[t];
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+            const int bin = (t * kEpiK + kC) * kEpiK + kC;
+            if (lane == 0 && v) atomicAdd(&bins[bin >> 1], (unsigned)v << (16 * (bin & 1)));
+        }
+        __syncthreads();
+        const int nbins = ep.T * kEpiK * kEpiK;
+        unsigned long long* out = ep.hist + (long)blockIdx.y * nbins;
+        for (int i = threadIdx.x; 2 * i < nbins; i += 256) {
+            const unsigned w = bins[i];
+            if (w & 0xffffu) atomicAdd(out + 2 * i, (unsigned long long)(w & 0xffffu));
+            if (w >> 16) atomicAdd(out + 2 * i + 1, (unsigned long long)(w >> 16));   // (the odd bin past the end stays 0)
         }
     }
 }
@@ -718,8 +861,73 @@ extern "C" int ver_occ_mlp_forward_stats(const void* x, const void* image, const
     long grid = (nblk + 3) / 4;
     if (grid > 512) grid = 512;                            // 2 workgroups per CU, persistent
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, (const __bf16*)x,
-                       (const __bf16*)image, vectors, (__bf16*)logits, N, eps, rstd);
+                       (const __bf16*)image, vectors, (__bf16*)logits, N, eps, rstd, FwdEpilogue<kEpiLogits>{});
     return ver_check_launch("ver_occ_mlp_forward");
+}
+
+// ---- classification inside the forward kernel (ver_occ_mlp_confusion / ver_occ_mlp_classes) ---------------------------
+namespace {
+template <int EPI>
+int launch_fwd_epilogue(const char* who, const void* x, const void* image, const float* vectors, long N, float eps, int flags,
+                        dim3 grid, FwdEpilogue<EPI> ep, void* stream) {
+    const bool l1 = flags & 1, centered = flags & 2;
+    auto kern = l1 ? (centered ? k_occ_mlp_fwd<4, true, true, false, EPI> : k_occ_mlp_fwd<4, true, false, false, EPI>)
+                   : (centered ? k_occ_mlp_fwd<4, false, true, false, EPI> : k_occ_mlp_fwd<4, false, false, false, EPI>);
+    const size_t lds = (size_t)(l1 ? kFwdFrags : kF2 + (kFwdFrags - kF3)) * 1024 + kVecFloats * sizeof(float) +
+                       (EPI == kEpiConfusion ? kEpiBinWords * sizeof(unsigned) : 0);
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "%s: LDS attribute: %s", who, hipGetErrorString(e));
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, (hipStream_t)stream, (const __bf16*)x, (const __bf16*)image, vectors,
+                       (__bf16*)nullptr, N, eps, (float*)nullptr, ep);
+    return ver_check_launch(who);
+}
+}  // namespace
+
+extern "C" int ver_occ_mlp_confusion(const void* x, const void* image, const float* vectors, const uint8_t* labels,
+                                     long rows_per_sample, int samples, const float* thresholds, int num_thresholds,
+                                     int64_t* hist, int width, int classes, float eps, int flags, void* stream) {
+    const char* who = "ver_occ_mlp_confusion";
+    VER_REQUIRE(rows_per_sample >= 0 && samples >= 0, VER_EINVAL, "%s: bad shape rows_per_sample=%ld samples=%d", who,
+                rows_per_sample, samples);
+    VER_REQUIRE(width == kW && classes == kC, VER_EUNSUPPORTED, "%s: built for width %d / %d classes (got %d / %d)", who, kW,
+                kC, width, classes);
+    VER_REQUIRE((flags & ~3) == 0, VER_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    VER_REQUIRE(num_thresholds >= 1 && num_thresholds <= kEpiMaxT, VER_EUNSUPPORTED, "%s: %d thresholds (1 to %d)", who,
+                num_thresholds, kEpiMaxT);
+    if (rows_per_sample == 0 || samples == 0) return VER_OK;       // nothing to count: no pointer is looked at
+    int rc = check_common(who, x, image, vectors, rows_per_sample, width, classes);
+    if (rc) return rc;
+    VER_REQUIRE(thresholds && labels && hist, VER_EINVAL, "%s: null pointer argument", who);
+    VER_REQUIRE(((uintptr_t)hist & 7) == 0, VER_EINVAL, "%s: hist must be 8-byte aligned", who);
+    const long chunks = (rows_per_sample + kEpiChunkRows - 1) / kEpiChunkRows;
+    // (within these bounds every byte offset, sample * rows_per_sample * 256 + ..., is far inside 64 bits)
+    VER_REQUIRE(chunks < (1L << 31) && samples < 65536, VER_EUNSUPPORTED, "%s: %ld chunks per sample x %d samples exceed the grid",
+                who, chunks, samples);
+    FwdEpilogue<kEpiConfusion> ep = {};
+    ep.labels = labels;
+    ep.hist = reinterpret_cast<unsigned long long*>(hist);
+    for (int t = 0; t < num_thresholds; ++t) ep.thr[t] = thresholds[t];
+    ep.T = num_thresholds;
+    return launch_fwd_epilogue<kEpiConfusion>(who, x, image, vectors, rows_per_sample, eps, flags,
+                                              dim3((unsigned)chunks, (unsigned)samples), ep, stream);
+}
+
+extern "C" int ver_occ_mlp_classes(const void* x, const void* image, const float* vectors, uint8_t* cls, float* prob, long N,
+                                   float threshold, int width, int classes, float eps, int flags, void* stream) {
+    const char* who = "ver_occ_mlp_classes";
+    VER_REQUIRE(N >= 0, VER_EINVAL, "%s: negative row count", who);
+    VER_REQUIRE(width == kW && classes == kC, VER_EUNSUPPORTED, "%s: built for width %d / %d classes (got %d / %d)", who, kW,
+                kC, width, classes);
+    VER_REQUIRE((flags & ~3) == 0, VER_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    if (N == 0) return VER_OK;                                      // nothing to classify: no pointer is looked at
+    int rc = check_common(who, x, image, vectors, N, width, classes);
+    if (rc) return rc;
+    VER_REQUIRE(cls, VER_EINVAL, "%s: null class pointer", who);
+    VER_REQUIRE(((uintptr_t)prob & 3) == 0, VER_EINVAL, "%s: prob must be 4-byte aligned", who);
+    FwdEpilogue<kEpiClasses> ep = {cls, prob, threshold};
+    long grid = (N + 255) / 256;
+    if (grid > 512) grid = 512;                            // 2 workgroups per CU, persistent (as ver_occ_mlp_forward)
+    return launch_fwd_epilogue<kEpiClasses>(who, x, image, vectors, N, eps, flags, dim3((unsigned)grid), ep, stream);
 }
 
 extern "C" int ver_occ_mlp_backward(const void* x, const void* grad_logits, const void* image, const float* vectors,

@@ -9,7 +9,9 @@
 // exclusive scan over 1024-row blocks and one ordered compaction pass.  Integer results: bit-exact by construction
 // wherever the fp32 sigmoids of a row are distinct.
 // The evaluation metric (ver_occ_confusion: the confusion matrix of SSCMetrics) classifies rows with the same
-// row_argmax / threshold_class, so a prediction is the same function in both entry points.
+// row_argmax / threshold_class, so a prediction is the same function in both entry points; the per-element rule and
+// threshold_class live in ver_classify.h, which the classifying epilogues of the fused MLP forward share.
+#include "ver_classify.h"
 #include "ver_common.h"
 
 namespace {
@@ -38,8 +40,8 @@ __device__ __forceinline__ int row_argmax(const void* logits, long row, int C, f
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float p = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x[j])));
-            const bool take = (c0 + j == 0) || (p > pb) || (isnan(p) && !isnan(pb));
+            const float p = ver_class_prob(x[j]);
+            const bool take = (c0 + j == 0) || ver_class_takes(p, pb);
             if (take) {
                 best = c0 + j;
                 pb = p;
@@ -48,11 +50,6 @@ __device__ __forceinline__ int row_argmax(const void* logits, long row, int C, f
     }
     pb_out = pb;
     return best;
-}
-
-// the threshold is the LAST column: it wins only when strictly greater than every class probability
-__device__ __forceinline__ int threshold_class(int best, float pb, float thr, int C) {
-    return (!isnan(pb) && thr > pb) ? C : best;
 }
 
 template <bool BF16>

@@ -269,61 +269,80 @@ class VoxelFormerOccupancyHead(BaseModule):
         return (self.fuse_occ_mlp_loss and isinstance(lo, FocalLoss) and lo.use_sigmoid and lo.reduction == 'mean'
                 and occ_mlp_backward_takes_grad_scale())
 
+    def _volume_input(self, voxel_embed):
+        """The encoder output as the occupancy branch reads it: the bf16 side copy where there is one, contiguous."""
+        # under bf16 autocast the encoder's last LayerNorm wrote the bf16 copy of its output next to the fp32 one
+        # (bricks.residual_layer_norm): the lattice path would make exactly that copy again (and widen its gradient)
+        lowp = lowp_view(voxel_embed)
+        if lowp is not voxel_embed and lowp.shape == voxel_embed.shape and lowp.is_contiguous():
+            voxel_embed = lowp
+        return voxel_embed.contiguous()
+
+    def _occ_rows_from_lattice(self, voxel_embed):
+        """The lattice path of ``occupancy_from_volume`` up to the rows ``occ_branches`` reads: voxel_embed as
+        ``_volume_input`` returns it -> ``(rows [bs*X*Y, Z*occ_dims] in group-major GEMM order, plan, fold)``, or None
+        when the head's geometry takes the dense path.  ``fold``: ``occ_branches[0]`` was folded, centred, into
+        ``occ_proj`` -- the rows are ITS output and the MLP kernels start at the first LayerNorm."""
+        if not self.refine_occ:
+            return None
+        bs = voxel_embed.shape[0]
+        c = self.embed_dims
+        x = voxel_embed.view(bs, c, self.bev_z, self.bev_h, self.bev_w)          # raw view :558
+        convs = list(self.up_sample)
+        if (self.bev_z != self.occ_zdim and len(convs) == 3 and all(is_reference_geometry(m) for m in convs)
+                and 8 * self.bev_h == self.occ_xdim and 8 * self.bev_w == self.occ_ydim):
+            # lattice path: neither the dense volume nor its 3/4 constant columns are formed
+            e, b_up = upsample_lattice(x, [m.weight for m in convs], [m.bias for m in convs])
+            # ``occ_proj`` (:571) is followed by ``occ_branches[0]`` = Linear(128, 128) on every 128-slice of
+            # its output (:580) with nothing in between: on the fused bf16 path the two compose into ONE Linear,
+            # W' = (I_35 (x) W1) W_proj, b' = (I_35 (x) W1) b_proj + b1 (3.5 GFLOP per step, autograd maps the
+            # gradient of W' back onto both parameters), and the MLP kernels start at the first LayerNorm.
+            fold = self.fold_first_occ_linear and e.is_cuda and self._occ_mlp_runs_fused(e)
+            w_proj, b_proj = self.occ_proj.weight, self.occ_proj.bias
+            if fold:
+                l1 = self.occ_branches[0]
+                with torch.autocast('cuda', enabled=False):
+                    # ... and the Linear that feeds a LayerNorm is CENTRED over its output axis on the way
+                    # (W1 <- P W1, b1 <- P b1, P = I - 11^T/128): LN(Wx + b) = LN(PWx + Pb) exactly, the rows the
+                    # MLP kernel loads then have zero mean by construction and its LayerNorm skips the mean pass
+                    # (a quarter of the forward kernel's VALU work); autograd maps the gradients back through P
+                    w1c, b1c = self._centered(l1.weight.float(), l1.bias.float())
+                    # (a batched product over the 35 z-slices: ``matmul`` of a matrix with a 3-D tensor goes through
+                    #  transposed contiguous copies of the whole [35, 128, 3072] weight, forward and backward)
+                    w_proj = torch.bmm(w1c.expand(self.occ_zdim, *w1c.shape).contiguous(),
+                                       w_proj.float().view(self.occ_zdim, self.occ_dims, -1)).view_as(w_proj)
+                    b_proj = torch.addmm(b1c, b_proj.float().view(self.occ_zdim, self.occ_dims), w1c.t()).view(-1)
+            res = occ_proj_from_lattice(e, convs[-1].bias, w_proj, b_proj)
+            if res is not None:
+                return res[0], res[1], fold
+        return None
+
     def occupancy_from_volume(self, voxel_embed, rows_only=False, loss_targets=None):
         """voxel_embed [bs, Nq, C] (per-sample contiguous Nq*C buffer = the reference's
         ``bev_embed`` at bs=1) -> occupancy logits [bs, X*Y*Z, classes]   (head:554-580).
         ``rows_only`` (lattice path): return ``(logits [bs*X*Y, Z, classes] in GEMM row order, plan, bs)`` instead."""
         bs = voxel_embed.shape[0]
         c = self.embed_dims
-        # under bf16 autocast the encoder's last LayerNorm wrote the bf16 copy of its output next to the fp32 one
-        # (bricks.residual_layer_norm): the lattice path would make exactly that copy again (and widen its gradient)
-        lowp = lowp_view(voxel_embed)
-        if lowp is not voxel_embed and lowp.shape == voxel_embed.shape and lowp.is_contiguous():
-            voxel_embed = lowp
-        voxel_embed = voxel_embed.contiguous()
+        voxel_embed = self._volume_input(voxel_embed)
+        lattice = self._occ_rows_from_lattice(voxel_embed)
+        if lattice is not None:
+            # ``occ_branches`` is row-wise: run it on the rows as the GEMMs left them
+            # (group-major) and bring only the 8x narrower logits into the reference's
+            # (Z, X, Y) voxel order (:572-579)
+            rows, plan, fold = lattice
+            if (loss_targets is not None and fold and self._fused_loss_applies()
+                    and self.occupancy_classes == 16 and torch.is_grad_enabled()):
+                # training loss only: the MLP kernel's logits go straight into the focal-loss pass, which leaves
+                # the unscaled gradient in their place; the MLP backward reads it with the loss's scalar factor
+                # (hipops.OccMLPFocalLossFunction) -- no focal backward pass over the [N, 16] tensor
+                return self._occ_mlp_focal_loss(rows.view(-1, self.occ_dims), loss_targets, plan, bs)
+            logits = self._occ_mlp(rows.view(rows.shape[0], self.occ_zdim, self.occ_dims), first_folded=fold)
+            if rows_only:
+                return logits, plan, bs
+            logits = rows_to_voxels(logits, plan, bs)                       # [bs, X*Y, Z, classes]
+            return logits.permute(0, 2, 1, 3).reshape(bs, -1, logits.shape[-1])
         if self.refine_occ:
             x = voxel_embed.view(bs, c, self.bev_z, self.bev_h, self.bev_w)          # raw view :558
-            convs = list(self.up_sample)
-            if (self.bev_z != self.occ_zdim and len(convs) == 3 and all(is_reference_geometry(m) for m in convs)
-                    and 8 * self.bev_h == self.occ_xdim and 8 * self.bev_w == self.occ_ydim):
-                # lattice path: neither the dense volume nor its 3/4 constant columns are formed
-                e, b_up = upsample_lattice(x, [m.weight for m in convs], [m.bias for m in convs])
-                # ``occ_proj`` (:571) is followed by ``occ_branches[0]`` = Linear(128, 128) on every 128-slice of
-                # its output (:580) with nothing in between: on the fused bf16 path the two compose into ONE Linear,
-                # W' = (I_35 (x) W1) W_proj, b' = (I_35 (x) W1) b_proj + b1 (3.5 GFLOP per step, autograd maps the
-                # gradient of W' back onto both parameters), and the MLP kernels start at the first LayerNorm.
-                fold = self.fold_first_occ_linear and e.is_cuda and self._occ_mlp_runs_fused(e)
-                w_proj, b_proj = self.occ_proj.weight, self.occ_proj.bias
-                if fold:
-                    l1 = self.occ_branches[0]
-                    with torch.autocast('cuda', enabled=False):
-                        # ... and the Linear that feeds a LayerNorm is CENTRED over its output axis on the way
-                        # (W1 <- P W1, b1 <- P b1, P = I - 11^T/128): LN(Wx + b) = LN(PWx + Pb) exactly, the rows the
-                        # MLP kernel loads then have zero mean by construction and its LayerNorm skips the mean pass
-                        # (a quarter of the forward kernel's VALU work); autograd maps the gradients back through P
-                        w1c, b1c = self._centered(l1.weight.float(), l1.bias.float())
-                        # (a batched product over the 35 z-slices: ``matmul`` of a matrix with a 3-D tensor goes through
-                        #  transposed contiguous copies of the whole [35, 128, 3072] weight, forward and backward)
-                        w_proj = torch.bmm(w1c.expand(self.occ_zdim, *w1c.shape).contiguous(),
-                                           w_proj.float().view(self.occ_zdim, self.occ_dims, -1)).view_as(w_proj)
-                        b_proj = torch.addmm(b1c, b_proj.float().view(self.occ_zdim, self.occ_dims), w1c.t()).view(-1)
-                res = occ_proj_from_lattice(e, convs[-1].bias, w_proj, b_proj)
-                if res is not None:
-                    # ``occ_branches`` is row-wise: run it on the rows as the GEMMs left them
-                    # (group-major) and bring only the 8x narrower logits into the reference's
-                    # (Z, X, Y) voxel order (:572-579)
-                    rows, plan = res
-                    if (loss_targets is not None and fold and self._fused_loss_applies()
-                            and self.occupancy_classes == 16 and torch.is_grad_enabled()):
-                        # training loss only: the MLP kernel's logits go straight into the focal-loss pass, which leaves
-                        # the unscaled gradient in their place; the MLP backward reads it with the loss's scalar factor
-                        # (hipops.OccMLPFocalLossFunction) -- no focal backward pass over the [N, 16] tensor
-                        return self._occ_mlp_focal_loss(rows.view(-1, self.occ_dims), loss_targets, plan, bs)
-                    logits = self._occ_mlp(rows.view(rows.shape[0], self.occ_zdim, self.occ_dims), first_folded=fold)
-                    if rows_only:
-                        return logits, plan, bs
-                    logits = rows_to_voxels(logits, plan, bs)                       # [bs, X*Y, Z, classes]
-                    return logits.permute(0, 2, 1, 3).reshape(bs, -1, logits.shape[-1])
             x = self._upsample(x).contiguous()
             x = x.view(bs, self.bev_z, self.occ_xdim, self.occ_ydim, c)              # raw view :564
             ox, oy = self.occ_xdim, self.occ_ydim
@@ -777,6 +796,101 @@ class VoxelFormerOccupancyHead(BaseModule):
         if hist is None:
             hist = torch.zeros((bs, len(thresholds), nc + 1, nc + 1), dtype=torch.int64, device=occupancy_preds.device)
         return _confusion(occupancy_preds, labels, bs, thresholds, hist)
+
+    # ------------------------------------------------------------------ evaluation without logits
+    def _fused_eval_rows(self, voxel_embed):
+        """``(x bf16 [rows, 128], plan, bs)`` when the classifying MLP launches apply to this volume -- the lattice path
+        with the folded, centred first Linear (bf16 autocast on the GPU), 16 classes, no autograd -- else None."""
+        if torch.is_grad_enabled() or self.occupancy_classes != 16:
+            return None
+        lattice = self._occ_rows_from_lattice(self._volume_input(voxel_embed))
+        if lattice is None or not lattice[2]:
+            return None
+        rows, plan, _ = lattice
+        return rows.view(-1, self.occ_dims).to(torch.bfloat16), plan, voxel_embed.shape[0]
+
+    def _fused_eval_params(self):
+        """(image, vectors, eps) of the classifying MLP launches for the folded, centred chain: what ``OccMLPFunction``
+        packs for ``_occ_mlp(first_folded=True)`` (W2 in W1's image section, b1 = 0)."""
+        from ..hipops import occ_mlp_pack, occ_mlp_vectors
+        _, n1, _, l2, n2, _, l3 = list(self.occ_branches)
+        with torch.autocast('cuda', enabled=False):
+            w2c, b2c = self._centered(l2.weight.float(), l2.bias.float())
+            image = occ_mlp_pack(w2c, w2c, l3.weight)
+            vec = occ_mlp_vectors(torch.zeros(128, device=w2c.device), n1.weight, n1.bias, b2c, n2.weight, n2.bias,
+                                  l3.bias)
+        return image, vec, n1.eps
+
+    def occupancy_confusion_from_volume(self, voxel_embed, labels, thresholds=(0.25,), hist=None):
+        """``occupancy_confusion(occupancy_from_volume(voxel_embed, rows_only=True), labels, thresholds, hist)`` -- the
+        same int64 [bs, T, K, K] histograms -- without the logits where the fused MLP applies (bf16 autocast on the GPU,
+        the lattice path, no autograd): the forward kernel classifies every row in its epilogue and counts the
+        (label, prediction) pairs itself, one ``ver_occ_mlp_confusion`` launch per row group.  Everywhere else (CPU
+        tensors, fp32, an ``occ_branches`` the kernel is not built for, gradients enabled) the two existing functions are
+        composed."""
+        thresholds = tuple(float(t) for t in thresholds)
+        nc = self.occupancy_classes
+
+        fused = self._fused_eval_rows(voxel_embed) if 1 <= len(thresholds) <= 8 else None
+        if fused is None:
+            preds = self.occupancy_from_volume(voxel_embed, rows_only=True)
+            return self.occupancy_confusion(preds, labels, thresholds, hist)
+        from ..hipops import occ_mlp_confusion
+        x, plan, bs = fused
+        image, vec, eps = self._fused_eval_params()
+        gt = labels.reshape(bs, self.occ_zdim, plan.rows).permute(0, 2, 1)          # (Z, X, Y) order -> [bs, X*Y, Z]
+        gt = voxels_to_rows(gt.to(torch.uint8), plan, bs)
+        if hist is None:
+            hist = torch.zeros((bs, len(thresholds), nc + 1, nc + 1), dtype=torch.int64, device=x.device)
+        z = self.occ_zdim
+        # the rows of sample b in group g are contiguous (GEMM row bs*offset_g + b*n_g + i, Z voxels each): one launch per group
+        for g in plan.groups:
+            lo, hi = bs * g.offset, bs * (g.offset + g.n_rows)
+            occ_mlp_confusion(x[lo * z:hi * z], image, vec, gt[lo:hi], thresholds, bs, hist, eps,
+                              first_linear=False, centered=True)
+        return hist
+
+    def _classes_from_logits(self, logits, threshold):
+        """uint8 class per row of logits [..., classes] under ``get_occupancy_prediction``'s rule; ``classes`` = empty."""
+        nc = self.occupancy_classes
+        lead = logits.shape[:-1]
+        flat = logits.reshape(-1, nc)
+        if flat.is_cuda and nc % 8 == 0:
+            from ..hipops import occ_predict
+            pairs = occ_predict(flat, threshold)
+            cls = torch.full((flat.shape[0],), nc, dtype=torch.uint8, device=flat.device)
+            cls[pairs[:, 0]] = pairs[:, 1].to(torch.uint8)
+            return cls.view(lead)
+        p = flat.float().sigmoid()
+        p = torch.cat((p, torch.ones_like(p)[:, :1] * threshold), dim=-1)
+        return p.argmax(dim=-1).to(torch.uint8).view(lead)
+
+    def occupancy_classes_from_volume(self, voxel_embed, threshold=0.25):
+        """The dense class map of ``get_occupancy_prediction``: uint8 [bs, X*Y*Z] in the reference's (Z, X, Y) voxel
+        order, ``occupancy_classes`` = empty.  Where the fused MLP applies (see ``occupancy_confusion_from_volume``) one
+        ``ver_occ_mlp_classes`` launch writes a byte per voxel and no logits; otherwise the classes of
+        ``occupancy_from_volume``'s logits."""
+        fused = self._fused_eval_rows(voxel_embed)
+        if fused is None:
+            return self._classes_from_logits(self.occupancy_from_volume(voxel_embed).detach(), threshold)
+        from ..hipops import occ_mlp_classes
+        x, plan, bs = fused
+        image, vec, eps = self._fused_eval_params()
+        cls = occ_mlp_classes(x, image, vec, threshold, eps=eps, first_linear=False, centered=True)
+        cls = rows_to_voxels(cls.view(-1, self.occ_zdim), plan, bs)                   # [bs, X*Y, Z]
+        return cls.permute(0, 2, 1).reshape(bs, -1)
+
+    def occupancy_pairs_from_classes(self, classes):
+        """Class map (``occupancy_classes_from_volume``) -> the sparse pairs of ``get_occupancy_prediction``: int64 [K, 2]
+        (voxel index over the flattened batch, class), ascending voxel index."""
+        flat = classes.reshape(-1)
+        occ_index, = torch.where(flat < self.occupancy_classes)
+        return torch.stack([occ_index, flat[occ_index].long()], dim=-1)
+
+    def get_occupancy_prediction_from_volume(self, voxel_embed, occ_threshold=0.25):
+        """``get_occupancy_prediction`` of ``occupancy_from_volume(voxel_embed)`` -- the same pairs -- through the class map."""
+        classes = self.occupancy_classes_from_volume(voxel_embed, occ_threshold)
+        return dict(occupancy_preds=self.occupancy_pairs_from_classes(classes), flow_preds=None)
 
     def loss_only_occupancy(self, gt_bboxes_list, gt_labels_list, gt_occupancy, preds_dicts):
         """``only_occ`` detectors (head:1387-1447): the occupancy focal loss alone, plus the zero ``loss_flow``."""

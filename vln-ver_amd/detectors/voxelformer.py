@@ -197,13 +197,21 @@ class VoxelFormer(BaseModule):
                 result_dict['pts_bbox'] = pts_bbox
         return new_prev_bev, bbox_list, occ_results
 
-    def evaluate_occupancy(self, img_metas, metrics=None, thresholds=(0.25,), autocast_dtype=None):
+    # what ``evaluate_occupancy(fused=None)`` resolves to.  Measured: the fused launch ties with the
+    # two-kernel path at one threshold and is 2 % slower at eight, so the default stays on the logits path; ``fused=True``
+    # is for callers who want the 3.1 GB of logits not to be allocated.
+    fused_occupancy_eval = False
+
+    def evaluate_occupancy(self, img_metas, metrics=None, thresholds=(0.25,), autocast_dtype=None, fused=None):
         """The occupancy evaluation of ``simple_test`` followed by ``MP3DDataset.evaluate_occ_iou``
         (mp3docc_dataset.py:485-584) for a batch of viewpoints, on the device: the lifting path alone (no decoder, logits
         left in the GEMMs' row order), labels from each meta's ``occ_gt_path`` (sparse (index, class) pairs) and optional
         ``occ_invalid_path`` (voxel indices outside the visible mask), the confusion matrices of every threshold
         counted into ``metrics`` (an ``occupancy_metrics.DeviceSSCMetrics``; a new one with ``thresholds`` when None;
-        its own thresholds otherwise).  ``autocast_dtype``: 'bf16' runs the path under bf16 autocast.  -> ``metrics``."""
+        its own thresholds otherwise).  ``autocast_dtype``: 'bf16' runs the path under bf16 autocast.  ``fused``: True
+        counts inside the MLP forward kernel where that applies (bf16 autocast on the GPU: no logits are written;
+        ``head.occupancy_confusion_from_volume``), False always goes through the logits, None = ``fused_occupancy_eval``;
+        the histograms are the same either way, and fp32 callers take the logits path whatever the value.  -> ``metrics``."""
         from ..occupancy_metrics import DeviceSSCMetrics
         head = self.pts_bbox_head
         dev = self._device()
@@ -216,6 +224,8 @@ class VoxelFormer(BaseModule):
         labels = head.occupancy_eval_labels(occ_gts, invalid, device=dev)
         with torch.no_grad(), torch.autocast('cuda', dtype=lowp or torch.bfloat16, enabled=lowp is not None and img_feats.is_cuda):
             voxel_embed = head(img_feats, img_metas, only_bev=True)
+            if self.fused_occupancy_eval if fused is None else fused:
+                return metrics.add_volume(head, voxel_embed, labels)
             preds = head.occupancy_from_volume(voxel_embed, rows_only=True)
         metrics.add(head, preds, labels)
         return metrics

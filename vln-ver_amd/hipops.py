@@ -1260,6 +1260,57 @@ def occ_confusion(logits, labels, thresholds=(0.25,), samples=1, hist=None):
     return hist
 
 
+def _occ_mlp_eval_args(who, x, image, vectors):
+    """Checked inputs of the classifying forward launches: x bf16 [N, 128] contiguous; inference only."""
+    x = _gpu(x, 'x')
+    if x.dtype != torch.bfloat16 or x.shape[-1] != 128:
+        raise TypeError('x must be bf16 [..., 128]')
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, image, vectors)):
+        raise RuntimeError('%s has no backward pass: call it under torch.no_grad()' % who)
+    return x.contiguous().view(-1, 128)
+
+
+def occ_mlp_confusion(x, image, vectors, labels, thresholds=(0.25,), samples=1, hist=None, eps=1e-5, first_linear=True,
+                      centered=False):
+    """``occ_confusion(occ_mlp_forward(x, image, vectors, ...), labels, thresholds, samples, hist)`` in ONE launch that
+    writes no logits (ver_occ_mlp_confusion): x bf16 [samples * rows, 128], labels u8 one per row -> int64 hist
+    [samples, T, 17, 17], accumulated into ``hist`` when given.  Exactly the counts of the two-kernel pair.  ``no_grad`` only."""
+    x = _occ_mlp_eval_args('occ_mlp_confusion', x, image, vectors)
+    n = x.shape[0]
+    labels = _gpu(labels, 'labels', torch.uint8).reshape(-1).contiguous()
+    if labels.numel() != n:
+        raise ValueError('occ_mlp_confusion: %d labels for %d rows' % (labels.numel(), n))
+    if samples < 1 or n % samples:
+        raise ValueError('occ_mlp_confusion: %d rows do not split into %d samples' % (n, samples))
+    thr = [float(t) for t in thresholds]
+    shape = (samples, len(thr), 17, 17)
+    if hist is None:
+        hist = torch.zeros(shape, dtype=torch.int64, device=x.device)
+    elif (tuple(hist.shape) != shape or hist.dtype != torch.int64 or not hist.is_contiguous() or hist.device != x.device):
+        raise ValueError('occ_mlp_confusion: hist must be a contiguous int64 %s tensor on %s' % (shape, x.device))
+    host_thr = (ctypes.c_float * max(len(thr), 1))(*thr)
+    _launch('ver_occ_mlp_confusion', lambda: lib().ver_occ_mlp_confusion(
+        _p(x), _p(image), _p(vectors), _p(labels), n // samples, samples, host_thr, len(thr), _p(hist), 128, 16, eps,
+        (1 if first_linear else 0) | (2 if centered else 0), _stream()))
+    return hist
+
+
+def occ_mlp_classes(x, image, vectors, threshold=0.25, want_prob=False, eps=1e-5, first_linear=True, centered=False):
+    """The class of every row without its logits (ver_occ_mlp_classes): x bf16 [..., 128] -> uint8 [...]: the class
+    ``occ_predict(occ_mlp_forward(x, ...), threshold)`` pairs with the row, 16 for an empty one.  ``want_prob``: returns
+    ``(classes, prob f32 [...])``, the fp32 sigmoid of the best class.  ``no_grad`` only."""
+    lead = x.shape[:-1]
+    x = _occ_mlp_eval_args('occ_mlp_classes', x, image, vectors)
+    n = x.shape[0]
+    cls = torch.empty(n, dtype=torch.uint8, device=x.device)
+    prob = torch.empty(n, dtype=torch.float32, device=x.device) if want_prob else None
+    _launch('ver_occ_mlp_classes', lambda: lib().ver_occ_mlp_classes(
+        _p(x), _p(image), _p(vectors), _p(cls), _p(prob), n, float(threshold), 128, 16, eps,
+        (1 if first_linear else 0) | (2 if centered else 0), _stream()))
+    cls = cls.view(lead)
+    return (cls, prob.view(lead)) if want_prob else cls
+
+
 # ------------------------------------------------------------------------------------------
 LSA_MAX = 1024            # ver_lsa_solve: rows and column capacity of a problem
 

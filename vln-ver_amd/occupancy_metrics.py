@@ -70,6 +70,11 @@ class DeviceSSCMetrics:
         the row-order tuple), ``labels`` uint8 [bs, voxel_num] of ``head.occupancy_eval_labels``."""
         return self.add_hist(head.occupancy_confusion(occupancy_preds, labels, self.thresholds))
 
+    def add_volume(self, head, voxel_embed, labels):
+        """Count one batch from the encoder output itself: ``head.occupancy_confusion_from_volume`` (no logits where the
+        fused MLP applies, the same histograms everywhere)."""
+        return self.add_hist(head.occupancy_confusion_from_volume(voxel_embed, labels, self.thresholds))
+
     def add_hist(self, hist):
         """Add histograms [T, K, K] or per-sample [bs, T, K, K] (kept as ``last``)."""
         if hist.dim() == 4:
