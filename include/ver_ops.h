@@ -442,12 +442,11 @@ int ver_occ_mlp_backward(const void* x, const void* grad_logits, const void* ima
  *   (no image), `vectors` as above (b1 is ignored).
  *     param_grads f32 [6*128 + 16*128 + 16 + 128*128]   d gamma1, d beta1, (unused), d gamma2, d beta2, d b2, then
  *                                               d W3 [16,128], d b3 [16], d W2 [128,128] -- natural order; zeroed inside
- */
-/*   flags: 0 or VER_OCC_MLP_CENTERED (the forward ran centred: W2 / b2 passed here are the centred ones, the recomputed
+ *   flags: 0 or VER_OCC_MLP_CENTERED (the forward ran centred: W2 / b2 passed here are the centred ones, the recomputed
  *   LayerNorm-forward steps skip the mean pass).
- */
-/*   grad_scale: NULL, or a DEVICE scalar that multiplies grad_logits as it is read (the gradient of the loss sum that
+ *   grad_scale: NULL, or a DEVICE scalar that multiplies grad_logits as it is read (the gradient of the loss sum that
  *   `ver_focal_loss_forward_grad` left unscaled: the training loss then needs no backward pass over the logits).
+ *   Always accepted: one kernel serves every combination of flags, grad_scale and rstd.
  */
 int ver_occ_mlp_backward_fused(const void* x, const void* grad_logits, const float* W2, const float* W3,
                                const float* vectors, void* grad_x, float* param_grads, long N, int width,

@@ -262,12 +262,8 @@ class VoxelFormerOccupancyHead(BaseModule):
         """The occupancy term is mmdet's sigmoid FocalLoss with mean reduction (vocc.py:190-195): the form the fused
         MLP + focal-loss Function evaluates."""
         from .losses import FocalLoss
-        from ..hipops import occ_mlp_backward_takes_grad_scale
         lo = self.loss_occupancy
-        # (the fused Function hands the backward kernel a device-side scale of d(logits): only the wave-specialised
-        #  kernel takes one -- under the A/B switch VER_OCC_MLP_WS=0 the loss goes through the logits as two ops)
-        return (self.fuse_occ_mlp_loss and isinstance(lo, FocalLoss) and lo.use_sigmoid and lo.reduction == 'mean'
-                and occ_mlp_backward_takes_grad_scale())
+        return self.fuse_occ_mlp_loss and isinstance(lo, FocalLoss) and lo.use_sigmoid and lo.reduction == 'mean'
 
     def _volume_input(self, voxel_embed):
         """The encoder output as the occupancy branch reads it: the bf16 side copy where there is one, contiguous."""

@@ -876,9 +876,14 @@ def occ_mlp_vectors(b1, g1, be1, b2, g2, be2, b3):
     return vec.contiguous()
 
 
-# 1 (default): on centred rows the forward kernel saves 1/std of both LayerNorms per row (8 B on 288 B of traffic) and the
-# wave-specialised backward kernel reads them back instead of recomputing the statistics; 0: recompute (round-4 form)
-_OCC_MLP_SAVE_RSTD = os.environ.get('VER_OCC_MLP_SAVE_RSTD', '1') == '1'
+# True: on centred rows the forward kernel saves 1/std of both LayerNorms per row (8 B on 288 B of traffic) and the fused
+# backward kernel reads them back instead of recomputing the statistics.  False selects the recomputing form of that kernel
+# on centred rows too (test_occ_mlp_backward_with_saved_statistics_equals_the_recomputing_kernel compares the two).
+_OCC_MLP_SAVE_RSTD = True
+# True: the folded MLP's backward is ver_occ_mlp_backward_fused.  False selects the row-split kernel + host GEMM for d(W2),
+# the only backward of the unfolded MLP (test_occ_mlp_fused_with_folded_first_linear and
+# test_occ_mlp_backward_kernels_on_ragged_sizes run both as each other's second opinion).
+_OCC_MLP_BWD_FUSED = True
 
 
 def occ_mlp_forward(x, image, vectors, eps=1e-5, first_linear=True, centered=False, want_rstd=False):
@@ -900,36 +905,54 @@ def occ_mlp_forward(x, image, vectors, eps=1e-5, first_linear=True, centered=Fal
 
 
 def _occ_mlp_wants_rstd(folded, centered, n):
-    return bool(_OCC_MLP_SAVE_RSTD and folded and centered and _OCC_MLP_BWD_FUSED and occ_mlp_backward_takes_grad_scale()
-                and n < (1 << 28))
+    return bool(_OCC_MLP_SAVE_RSTD and _OCC_MLP_BWD_FUSED and folded and centered and n < (1 << 28))
 
 
-def _rows_tn(a, b, chunk=8000, with_colsum=True):
-    """a^T b in fp32 for tall a [N,P], b [N,Q] (N ~ 1e7, P,Q <= 128) plus the column sums of a:
-    the row dimension is split into chunks run as ONE batched GEMM (a plain GEMM would own a
-    single output tile and run on one CU)."""
+def _occ_mlp_forward_packed(x, w1, b1, g1, be1, w2, b2, g2, be2, w3, b3, eps, centered, save_rstd):
+    """Pack the fragment image and the vectors, run the forward (w1 None: folded first Linear) and, where ``save_rstd`` and the
+    backward will read them, keep the LayerNorm statistics: ``(image, vec, logits, rstd or None)``."""
+    folded = w1 is None
+    if folded:
+        # (the folded kernels read W2 from W1's image sections: natural k order forward, natural-order output rows
+        #  in the dgrad -- the layouts a chain that starts with a LayerNorm on the loaded rows needs)
+        w1, b1 = w2, torch.zeros(128, device=x.device)
+    image = occ_mlp_pack(w1, w2, w3)
+    vec = occ_mlp_vectors(b1, g1, be1, b2, g2, be2, b3)
+    has_rstd = save_rstd and _occ_mlp_wants_rstd(folded, centered, x.numel() // 128)
+    out = occ_mlp_forward(x, image, vec, eps, first_linear=not folded, centered=centered, want_rstd=has_rstd)
+    logits, rstd = out if has_rstd else (out, None)
+    return image, vec, logits, rstd
+
+
+def _occ_mlp_backward_fused(x2, gl, w2, w3, vec, rstd, eps, centered, gscale):
+    """ver_occ_mlp_backward_fused_stats on rows x2 [N,128], d(logits) gl [N,16] (times the device scalar ``gscale`` if given):
+    d(W2) and every other parameter gradient accumulated in the kernel, no side tensors.  Returns
+    ``(gx, vecs [6,128] = d gamma1, d beta1, -, d gamma2, d beta2, d b2, dw2, dw3, db3)``."""
+    n = x2.shape[0]
+    gx = torch.empty_like(x2)
+    pg = torch.empty(6 * 128 + 16 * 128 + 16 + 128 * 128, dtype=torch.float32, device=x2.device)
+    _launch('ver_occ_mlp_backward_fused', lambda: lib().ver_occ_mlp_backward_fused_stats(
+        _p(x2), _p(gl), _p(w2.float().contiguous()), _p(w3.float().contiguous()), _p(vec),
+        _p(rstd), _p(gx), _p(pg), n, 128, 16, eps, _p(gscale), 2 if centered else 0, _stream()))
+    vecs = pg[:768].view(6, 128)
+    dw3 = pg[768:768 + 2048].view(16, 128)
+    db3 = pg[768 + 2048:768 + 2048 + 16]
+    dw2 = pg[768 + 2048 + 16:].view(128, 128)
+    return gx, vecs, dw2, dw3, db3
+
+
+def _rows_tn(a, b, chunk=8000):
+    """a^T b in fp32 for tall a [N,P], b [N,Q] (N ~ 1e7, P,Q <= 128): the row dimension is split into chunks run as ONE
+    batched GEMM (a plain GEMM would own a single output tile and run on one CU)."""
     n = a.shape[0]
     s = n // chunk
     main = s * chunk
     prod = a.new_zeros((a.shape[1], b.shape[1]), dtype=torch.float32)
-    colsum = a.new_zeros((a.shape[1],), dtype=torch.float32)
     if s:
-        a3 = a[:main].view(s, chunk, -1)
-        prod += torch.bmm(a3.transpose(1, 2), b[:main].view(s, chunk, -1)).sum(0, dtype=torch.float32)
-        if with_colsum:
-            ones = a.new_ones((1, 1, chunk)).expand(s, 1, chunk)
-            colsum += torch.bmm(ones, a3).sum((0, 1), dtype=torch.float32)
+        prod += torch.bmm(a[:main].view(s, chunk, -1).transpose(1, 2), b[:main].view(s, chunk, -1)).sum(0, dtype=torch.float32)
     if main < n:
         prod += (a[main:].t() @ b[main:]).float()
-        if with_colsum:
-            colsum += a[main:].sum(0, dtype=torch.float32)
-    return prod, colsum
-
-
-def occ_mlp_backward_takes_grad_scale():
-    """True when ``ver_occ_mlp_backward_fused`` runs the wave-specialised kernel, the one that takes ``grad_scale``
-    (VER_OCC_MLP_WS, read once by the library too: 0 selects the phase-locked N-split kernel, which rejects it)."""
-    return os.environ.get('VER_OCC_MLP_WS', '1') not in ('0',)
+    return prod
 
 
 _FRAG_ORDER = {}
@@ -948,9 +971,6 @@ def _frag_order(device):
     return _FRAG_ORDER[key]
 
 
-_OCC_MLP_BWD_FUSED = os.environ.get('VER_OCC_MLP_BWD_FUSED', '1') == '1'      # (0: row-split kernel + host GEMM for d(W2))
-
-
 class OccMLPFunction(Function):
     """``occ_branches`` (head:241-248) as one fused kernel each way (ver_occ_mlp_*): x bf16 [N,128]
     -> logits bf16 [N,16].  Nothing but x is kept for the backward pass (the chain is re-computed)."""
@@ -962,16 +982,10 @@ class OccMLPFunction(Function):
         # VoxelFormerOccupancyHead.occupancy_from_volume); the kernels then run it as the identity and its weight
         # gradient -- a [128, N] x [N, 128] product over all rows -- is not formed here at all
         ctx.folded = w1 is None
-        if ctx.folded:
-            # (the folded kernels read W2 from W1's image sections: natural k order forward, natural-order output rows
-            #  in the dgrad -- the layouts a chain that starts with a LayerNorm on the loaded rows needs)
-            w1, b1 = w2, torch.zeros(128, device=x.device)
-        image = occ_mlp_pack(w1, w2, w3)
-        vec = occ_mlp_vectors(b1, g1, be1, b2, g2, be2, b3)
         ctx.eps, ctx.centered = eps, bool(centered)
-        ctx.has_rstd = _occ_mlp_wants_rstd(ctx.folded, centered, x.numel() // 128) and any(ctx.needs_input_grad)
-        out = occ_mlp_forward(x, image, vec, eps, first_linear=not ctx.folded, centered=centered, want_rstd=ctx.has_rstd)
-        logits, rstd = out if ctx.has_rstd else (out, None)
+        image, vec, logits, rstd = _occ_mlp_forward_packed(x, w1, b1, g1, be1, w2, b2, g2, be2, w3, b3, eps, centered,
+                                                           save_rstd=any(ctx.needs_input_grad))
+        ctx.has_rstd = rstd is not None
         ctx.save_for_backward(x, image, vec, w2.detach(), w3.detach(), *((rstd,) if ctx.has_rstd else ()))
         return logits
 
@@ -984,18 +998,8 @@ class OccMLPFunction(Function):
         x2 = x.view(-1, 128)
         n = x2.shape[0]
         gl = _gpu(grad_logits, 'grad_logits').to(torch.bfloat16).contiguous().view(n, 16)
-        gscale = None
         if ctx.folded and _OCC_MLP_BWD_FUSED:
-            # N-split kernel: d(W2) and every other parameter gradient accumulated in the kernel, no side tensors
-            gx = torch.empty_like(x2)
-            pg = torch.empty(6 * 128 + 16 * 128 + 16 + 128 * 128, dtype=torch.float32, device=x.device)
-            _launch('ver_occ_mlp_backward_fused', lambda: lib().ver_occ_mlp_backward_fused_stats(
-                _p(x2), _p(gl), _p(w2.float().contiguous()), _p(w3.float().contiguous()), _p(vec),
-                _p(rstd), _p(gx), _p(pg), n, 128, 16, ctx.eps, _p(gscale), 2 if ctx.centered else 0, _stream()))
-            vecs = pg[:768].view(6, 128)
-            dw3 = pg[768:768 + 2048].view(16, 128)
-            db3 = pg[768 + 2048:768 + 2048 + 16]
-            dw2 = pg[768 + 2048 + 16:].view(128, 128)
+            gx, vecs, dw2, dw3, db3 = _occ_mlp_backward_fused(x2, gl, w2, w3, vec, rstd, ctx.eps, ctx.centered, None)
             return (gx.view(shape), None, None, vecs[0], vecs[1], dw2, vecs[5], vecs[3], vecs[4], dw3, db3, None, None)
         gx, ga2, h1 = (torch.empty_like(x2) for _ in range(3))
         ga1 = None if ctx.folded else torch.empty_like(x2)
@@ -1007,12 +1011,12 @@ class OccMLPFunction(Function):
         vecs = pg[:768].view(6, 128)
         dw3 = pg[768:768 + 2048].view(16, 128)
         db3 = pg[768 + 2048:]
-        dw2, _ = _rows_tn(ga2, h1, with_colsum=False)
+        dw2 = _rows_tn(ga2, h1)
         if ctx.folded:                               # h1 comes back in natural feature order
             dw2 = dw2.index_select(0, inv)
             return (gx.view(shape), None, None, vecs[0], vecs[1], dw2, vecs[5], vecs[3], vecs[4], dw3, db3, None, None)
         dw2 = dw2.index_select(0, inv).index_select(1, inv)
-        dw1, _ = _rows_tn(ga1, x2, with_colsum=False)
+        dw1 = _rows_tn(ga1, x2)
         dw1 = dw1.index_select(0, inv)
         return (gx.view(shape), dw1, vecs[2], vecs[0], vecs[1], dw2, vecs[5], vecs[3], vecs[4], dw3, db3, None, None)
 
@@ -1027,11 +1031,9 @@ class OccMLPFocalLossFunction(Function):
     @staticmethod
     def forward(ctx, x, g1, be1, w2, b2, g2, be2, w3, b3, target, eps, gamma, alpha, centered):
         x = _gpu(x, 'x').contiguous()
-        image = occ_mlp_pack(w2, w2, w3)
-        vec = occ_mlp_vectors(torch.zeros(128, device=x.device), g1, be1, b2, g2, be2, b3)
-        ctx.has_rstd = _occ_mlp_wants_rstd(True, centered, x.numel() // 128)
-        out = occ_mlp_forward(x, image, vec, eps, first_linear=False, centered=centered, want_rstd=ctx.has_rstd)
-        logits, rstd = out if ctx.has_rstd else (out, None)
+        _, vec, logits, rstd = _occ_mlp_forward_packed(x, None, None, g1, be1, w2, b2, g2, be2, w3, b3, eps, centered,
+                                                       save_rstd=True)
+        ctx.has_rstd = rstd is not None
         l2 = logits.view(-1, 16)
         n = l2.shape[0]
         target = _gpu(target, 'target')
@@ -1056,20 +1058,9 @@ class OccMLPFocalLossFunction(Function):
     def backward(ctx, grad_out):
         x, vec, w2, w3, gl = ctx.saved_tensors[:5]
         rstd = ctx.saved_tensors[5] if ctx.has_rstd else None
-        shape = x.shape
-        x2 = x.view(-1, 128)
-        n = x2.shape[0]
         gscale = _gpu(grad_out, 'grad_out').float().reshape(1).contiguous()
-        gx = torch.empty_like(x2)
-        pg = torch.empty(6 * 128 + 16 * 128 + 16 + 128 * 128, dtype=torch.float32, device=x.device)
-        _launch('ver_occ_mlp_backward_fused', lambda: lib().ver_occ_mlp_backward_fused_stats(
-            _p(x2), _p(gl), _p(w2.float().contiguous()), _p(w3.float().contiguous()), _p(vec),
-            _p(rstd), _p(gx), _p(pg), n, 128, 16, ctx.eps, _p(gscale), 2 if ctx.centered else 0, _stream()))
-        vecs = pg[:768].view(6, 128)
-        dw3 = pg[768:768 + 2048].view(16, 128)
-        db3 = pg[768 + 2048:768 + 2048 + 16]
-        dw2 = pg[768 + 2048 + 16:].view(128, 128)
-        return (gx.view(shape), vecs[0], vecs[1], dw2, vecs[5], vecs[3], vecs[4], dw3, db3, None, None, None, None, None)
+        gx, vecs, dw2, dw3, db3 = _occ_mlp_backward_fused(x.view(-1, 128), gl, w2, w3, vec, rstd, ctx.eps, ctx.centered, gscale)
+        return (gx.view(x.shape), vecs[0], vecs[1], dw2, vecs[5], vecs[3], vecs[4], dw3, db3, None, None, None, None, None)
 
 
 def occ_mlp_focal_loss_sum(x, g1, be1, w2, b2, g2, be2, w3, b3, target, eps=1e-5, gamma=2.0, alpha=0.25, centered=False):
