@@ -684,6 +684,63 @@ int ver_det_match(const float* pred_boxes, const int32_t* pred_labels, const flo
                   const float* thresholds, int num_thresholds, float* iou_max, int32_t* gt_index,
                   uint8_t* tp_bits, int64_t* npos, int num_classes, int S, int Pcap, int Gcap, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Detection set loss on the device (additive to ABI 31; csrc/ver_setloss.hip): with ver_lsa_solve between the first and the
+ * second, these three take the decoder's outputs of ALL layers and samples to the matching costs, the per-layer focal and L1
+ * sums and their gradients -- what the head's _assignment_costs, _targets_from_match and _losses_from_targets (and autograd
+ * behind them) do in about fifty small torch launches (loss_single of the reference, head:903-976, per decoder layer).
+ * Shared operands:
+ *   cls          f32 | bf16 [L, B, Q, C] class logits (cls_dtype = VER_F32 | VER_BF16), or NULL: the room-layout form
+ *                (assign(..., layout=True), head:760-841), regression terms alone; gt_labels may then be NULL too
+ *   box          f32 [L, B, Q, box_ld] box codes, row pitch box_ld
+ *   gt           f32 [B, Gcap, 9]      gravity centre, dims, yaw, velocity; rows >= counts[b] are padding, never read
+ *   gt_labels    i64 [B, Gcap]
+ *   counts       i32 device [B]        valid boxes of sample b (clamped to [0, Gcap])
+ * n = normalize_bbox(gt) = (cx, cy, log w, log l, cz, log h, sin yaw, cos yaw, vx, vy).
+ *
+ * ver_det_costs: cost f32 [L, B, Q, Gcap], WRITTEN IN FULL; columns g >= counts[b] get 0.  For a valid column
+ *     cost = w_cls * (pos - neg)[gt_labels[b, g]] + w_reg * sum_{k<8} |box_k - n_k|
+ *     p = sigmoid(logit) in fp32;  pos = -log(p + eps) alpha (1 - p)^gamma;  neg = -log(1 - p + eps) (1 - alpha) p^gamma
+ *   (FocalLossCost + BBox3DL1Cost as HungarianAssigner3D.assign states them); non-finite entries of n count as 0, as the
+ *   nan_to_num of _assignment_costs does.  1 - p is formed without a subtraction (from exp(-|logit|)), so the cost stays
+ *   finite and accurate where the fp32 torch chain's 1 - p has rounded to 0.  A label outside [0, C) in a valid column gives
+ *   a NaN cost (the solver then flags the problem).  box_ld >= 8.
+ *   One workgroup per (layer, sample); one launch, no memset node, no allocation, no host read; an empty dimension (L, B, Q
+ *   or Gcap == 0) launches nothing.  Supported: Q, Gcap <= 1024 (the solver's limits), C <= 64; VER_EUNSUPPORTED beyond.
+ *
+ * ver_det_set_loss_forward: match i32 [L, B, Q] as ver_lsa_solve writes it; code_weights f32 [10]; sums f32 [2, L] and
+ *   npos i32 [L], both WRITTEN, not accumulated.  Row (l, b, q): label = gt_labels[b, match] when match >= 0, else C
+ *   (background, an all-zero one-hot).
+ *     sums[0, l] = sum over the layer's rows and C logits of the sigmoid focal loss, losses.sigmoid_focal_loss element for
+ *                  element: bce_with_logits(x, t) (alpha t + (1 - alpha)(1 - t)) pt^gamma, fp32 arithmetic (log1pf, IEEE
+ *                  division) on bf16 logits too; 0 in the layout form
+ *     sums[1, l] = sum of keep * code_weights[k] * |box_k - n_k| over k < 10, keep = matched AND all ten n_k finite (the
+ *                  rows the reference drops by boolean indexing)
+ *     npos[l]    = rows with match >= 0, whatever keep says
+ *   The sums are bit-reproducible from run to run: one workgroup per layer, a fixed reduction order, no float atomics.
+ *   A match outside [-1, counts[b]), or a matched label outside [0, C), makes that layer's two sums NaN and ORs 1 into
+ *   `bad` (i32 device scalar or NULL; never cleared here); the other layers are unaffected.  box_ld >= 10.
+ *   One launch, no memset node, no allocation, no host read.  L == 0 launches nothing.
+ *
+ * ver_det_set_loss_backward: the same operands; scale f32 DEVICE [2, L]; grad_cls in the dtype of cls [L, B, Q, C] (NULL in
+ *   the layout form); grad_box f32 [L, B, Q, box_ld]; both WRITTEN IN FULL.
+ *     grad_cls   = scale[0, l] * d focal / d logit
+ *     grad_box_k = scale[1, l] * keep * code_weights[k] * sign(box_k - n_k), sign(0) = 0; 0 for k >= 10 and rows not kept
+ *   The per-row terms are recomputed, nothing is saved by the forward.  A layer whose scale entry is exactly 0 gets exact
+ *   zeros, even where its logits or codes are NaN; a row the forward flags counts as background / not kept.  One launch.
+ */
+int ver_det_costs(const void* cls, int cls_dtype, const float* box, int box_ld, const float* gt,
+                  const int64_t* gt_labels, const int32_t* counts, float* cost, int L, int B, int Q, int C, int Gcap,
+                  float w_cls, float alpha, float gamma, float eps, float w_reg, void* stream);
+int ver_det_set_loss_forward(const void* cls, int cls_dtype, const float* box, int box_ld, const int32_t* match,
+                             const float* gt, const int64_t* gt_labels, const int32_t* counts,
+                             const float* code_weights, float* sums, int32_t* npos, int32_t* bad, int L, int B, int Q,
+                             int C, int Gcap, float alpha, float gamma, void* stream);
+int ver_det_set_loss_backward(const void* cls, int cls_dtype, const float* box, int box_ld, const int32_t* match,
+                              const float* gt, const int64_t* gt_labels, const int32_t* counts,
+                              const float* code_weights, const float* scale, void* grad_cls, float* grad_box, int L,
+                              int B, int Q, int C, int Gcap, float alpha, float gamma, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

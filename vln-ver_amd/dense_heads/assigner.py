@@ -5,7 +5,9 @@ core/bbox/assigners/hungarian_assigner_3d.py:16-143 and core/bbox/match_costs/ma
 ``FocalLossCost`` / ``IoUCost`` / the pseudo sampler are restated from mmdet 2.14.0 (SURVEY.md
 B.12).  By default the matching itself stays on the host (scipy ``linear_sum_assignment`` on a 100 x G cost
 matrix), as in the reference; ``HungarianAssigner3D(solver='device')`` solves it with ``hipops.lsa_solve`` instead
-(no device -> host round trip; among several optima of EQUAL cost its choice may differ from scipy's)."""
+(no device -> host round trip; among several optima of EQUAL cost its choice may differ from scipy's);
+``solver='fused'`` does the same here and makes the head form costs, targets, losses and gradients in the set-loss kernels
+(``hipops.det_costs`` / ``det_set_loss``) around that one solve."""
 import torch
 
 from ..registry import BBOX_ASSIGNERS, MATCH_COST, build_from_cfg
@@ -69,7 +71,7 @@ class HungarianAssigner3D:
     def __init__(self, cls_cost=dict(type='ClassificationCost', weight=1.),
                  reg_cost=dict(type='BBoxL1Cost', weight=1.0), iou_cost=dict(type='IoUCost', weight=0.0),
                  pc_range=None, solver='host'):
-        if solver not in ('host', 'device'):
+        if solver not in ('host', 'device', 'fused'):
             raise ValueError("HungarianAssigner3D: solver must be 'host' or 'device', got %r" % (solver,))
         self.solver = solver
         self.cls_cost = build_from_cfg(cls_cost, MATCH_COST)
@@ -88,7 +90,7 @@ class HungarianAssigner3D:
             return AssignResult(num_gts, gt_inds, None, labels=labels)
         reg_cost = self.reg_cost(bbox_pred[:, :8], normalize_bbox(gt_bboxes, self.pc_range)[:, :8])
         cost = reg_cost if layout else self.cls_cost(cls_pred, gt_labels) + reg_cost
-        if self.solver == 'device' and cost.is_cuda:
+        if self.solver in ('device', 'fused') and cost.is_cuda:      # ('fused': the head's one-pass set loss; a single problem here)
             return self._assign_on_device(cost.detach().float(), num_gts, gt_labels)
         if linear_sum_assignment is None:
             raise ImportError('Please run "pip install scipy" to install scipy first.')

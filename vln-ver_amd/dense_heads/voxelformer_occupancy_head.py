@@ -681,37 +681,41 @@ class VoxelFormerOccupancyHead(BaseModule):
         ``loss_bbox``, ``loss_occupancy``, ``loss_flow`` (zero); earlier layers -> ``d{i}.loss_*``.
         gt_bboxes_list: per sample [G, 7..9] boxes (gravity centre + dims + yaw [+ vel]);
         gt_occupancy: int64 [bs, voxel_num] with ``occupancy_classes`` = empty.
-        With the assigner's ``solver='device'``, ``gt_bboxes_list`` may be a ``PaddedGts`` (``pad_gts``; ``gt_labels_list``
-        is then unused): the static-shape form, with which nothing between the predictions and the loss dict touches the
-        host; the two lists are padded here otherwise."""
+        With the assigner's ``solver='device'`` or ``'fused'``, ``gt_bboxes_list`` may be a ``PaddedGts`` (``pad_gts``;
+        ``gt_labels_list`` is then unused): the static-shape form, with which nothing between the predictions and the loss
+        dict touches the host; the two lists are padded here otherwise.  ``'fused'`` forms costs, targets, losses and their
+        gradients in the set-loss kernels (``_set_loss_fused``) instead of the torch chain."""
         all_cls, all_box = preds_dicts['all_cls_scores'], preds_dicts['all_bbox_preds']
         occ = preds_dicts['occupancy_preds']
         nl = len(all_cls)
         losses = {}
         pending = preds_dicts.get('pending_targets')
-        padded = labels = None
+        padded = labels = targets = per_layer = None        # per_layer: (loss_cls, loss_bbox) of every decoder layer
         if isinstance(gt_bboxes_list, PaddedGts) or self._device_solver():
             if not self._device_solver():
                 raise ValueError("loss: a PaddedGts needs train_cfg.assigner.solver = 'device'")
             gts = gt_bboxes_list if isinstance(gt_bboxes_list, PaddedGts) else self.pad_gts(gt_bboxes_list, gt_labels_list)
-            targets = self._targets_device(all_cls, all_box, gts)
+            if self._fused_solver():
+                per_layer = self._set_loss_fused(all_cls, all_box, gts, self.loss_bbox)
+            else:
+                targets = self._targets_device(all_cls, all_box, gts)
         elif pending is not None and pending.get('key') == tuple(id(g) for g in gt_bboxes_list):
             targets = self._targets_finish(pending)         # started in forward(), solved under the occupancy head
         else:
             padded, labels = self._prepare_gts(gt_bboxes_list, gt_labels_list, all_box.device)
             targets = self._batched_targets(all_cls, all_box, padded, labels)
-        if targets is not None:
+        if per_layer is None and targets is not None:
             # every decoder layer's classification / box terms in one pass over [L * bs * Nq] rows
-            all_lc, all_lb = self._losses_from_targets(all_cls, all_box, *targets)
-        elif padded is None:
+            per_layer = self._losses_from_targets(all_cls, all_box, *targets)
+        if per_layer is None and padded is None:
             padded, labels = self._prepare_gts(gt_bboxes_list, gt_labels_list, all_box.device)
         for lvl in range(nl):
             last = lvl == nl - 1
-            if targets is None:
+            if per_layer is None:
                 lc, lb, lo = self.loss_single(all_cls[lvl], all_box[lvl], occ if last else None, padded, labels,
                                               gt_occupancy if last else None)
             else:
-                lc, lb = all_lc[lvl], all_lb[lvl]
+                lc, lb = per_layer[0][lvl], per_layer[1][lvl]
                 lo = self.occupancy_loss(occ, gt_occupancy) if (last and occ is not None) else torch.zeros_like(lc)
             if last:
                 losses.update(loss_cls=lc, loss_bbox=lb, loss_occupancy=lo, loss_flow=torch.zeros_like(lc))
@@ -898,14 +902,25 @@ class VoxelFormerOccupancyHead(BaseModule):
         occupancy term."""
         all_cls, all_box = preds_dicts['all_cls_scores'], preds_dicts['all_bbox_preds']
         dev = all_box.device
-        if not isinstance(gt_bboxes_list, (list, tuple)):
-            gt_bboxes_list, gt_labels_list = [gt_bboxes_list], [gt_labels_list]
-        boxes = [self._boxes_as_tensor(b, dev) for b in gt_bboxes_list]
-        labels = [torch.as_tensor(x, device=dev).long() for x in gt_labels_list]
+        fused = None
+        if isinstance(gt_bboxes_list, PaddedGts):
+            if not self._fused_solver():
+                raise ValueError("loss_only_detection: a PaddedGts needs train_cfg.assigner.solver = 'fused'")
+            fused = self._set_loss_fused(all_cls, all_box, gt_bboxes_list, self.loss_bbox)
+        else:
+            if not isinstance(gt_bboxes_list, (list, tuple)):
+                gt_bboxes_list, gt_labels_list = [gt_bboxes_list], [gt_labels_list]
+            boxes = [self._boxes_as_tensor(b, dev) for b in gt_bboxes_list]
+            labels = [torch.as_tensor(x, device=dev).long() for x in gt_labels_list]
+            if self._fused_solver():                         # every layer in one pass, no round trip per (layer, sample)
+                fused = self._set_loss_fused(all_cls, all_box, self.pad_gts(boxes, labels), self.loss_bbox)
         nl = len(all_cls)
         losses = {}
         for lvl in range(nl):
-            lc, lb, _ = self.loss_single(all_cls[lvl], all_box[lvl], None, boxes, labels)
+            if fused is not None:
+                lc, lb = fused[0][lvl], fused[1][lvl]
+            else:
+                lc, lb, _ = self.loss_single(all_cls[lvl], all_box[lvl], None, boxes, labels)
             if lvl == nl - 1:
                 losses.update(loss_cls=lc, loss_bbox=lb)
             else:
@@ -936,6 +951,10 @@ class VoxelFormerOccupancyHead(BaseModule):
         layout queries.  -> (loss_cls, loss_bbox, loss_layout, loss_occupancy)."""
         loss_cls, loss_bbox, loss_occ = self.loss_single(cls_scores, bbox_preds, occupancy_preds, gt_bboxes_list,
                                                          gt_labels_list, gt_occupancy)
+        return loss_cls, loss_bbox, self._layout_term(layout_preds, gt_layout_list, loss_cls), loss_occ
+
+    def _layout_term(self, layout_preds, gt_layout_list, loss_cls):
+        """The layout term of ``loss_single_layout`` (head:1060-1104) for one decoder layer's layout boxes [bs, Nq, 10]."""
         out = [self._layout_targets_single(layout_preds[i], gt_layout_list[i]) for i in range(layout_preds.size(0))]
         layout_targets = torch.cat([o[0] for o in out], 0)
         layout_weights = torch.cat([o[1] for o in out], 0)
@@ -947,7 +966,7 @@ class VoxelFormerOccupancyHead(BaseModule):
         layout_weights = layout_weights * self.code_weights
         loss_layout = self.loss_layout(layout_preds[ok, :10], normalized[ok, :10], layout_weights[ok, :10],
                                        avg_factor=num_layout_pos)
-        return loss_cls, loss_bbox, torch.nan_to_num(loss_layout), loss_occ
+        return torch.nan_to_num(loss_layout)
 
     @staticmethod
     def _boxes_as_tensor(b, device):
@@ -977,11 +996,25 @@ class VoxelFormerOccupancyHead(BaseModule):
         labels = [torch.as_tensor(x, device=dev).long() for x in gt_labels_list]
         nl = len(all_cls)
         losses = {}
+        fused = None
+        if self._fused_solver():
+            # the detection terms of every layer in one pass; the last layer's layout term through the same kernels without
+            # class logits (cost, solve and loss of L = 1), its normaliser all-reduced on the device
+            fused = self._set_loss_fused(all_cls, all_box, self.pad_gts(boxes, labels), self.loss_bbox)
+            if all_box.is_cuda:
+                room = self.pad_gts(layouts, [g.new_zeros(g.shape[0], dtype=torch.long) for g in layouts])
+                fused_layout = self._set_loss_fused(None, all_layout[nl - 1:], room, self.loss_layout)[1][0]
+            else:
+                fused_layout = self._layout_term(all_layout[nl - 1], layouts, fused[0][nl - 1])
         for lvl in range(nl):
             last = lvl == nl - 1
-            lc, lb, ll, lo = self.loss_single_layout(all_cls[lvl], all_box[lvl], all_layout[lvl],
-                                                     occ if last else None, boxes, labels, layouts,
-                                                     gt_occupancy if last else None)
+            if fused is not None:
+                lc, lb, ll = fused[0][lvl], fused[1][lvl], fused_layout if last else None
+                lo = self.occupancy_loss(occ, gt_occupancy) if (last and occ is not None) else torch.zeros_like(lc)
+            else:
+                lc, lb, ll, lo = self.loss_single_layout(all_cls[lvl], all_box[lvl], all_layout[lvl],
+                                                         occ if last else None, boxes, labels, layouts,
+                                                         gt_occupancy if last else None)
             if last:
                 losses.update(loss_cls=lc, loss_bbox=lb, loss_occupancy=lo, loss_flow=torch.zeros_like(lc),
                               loss_layout=ll)
@@ -1129,7 +1162,40 @@ class VoxelFormerOccupancyHead(BaseModule):
 
     # ---- the same targets without the round trip (train_cfg.assigner.solver = 'device')
     def _device_solver(self):
-        return getattr(self.assigner, 'solver', 'host') == 'device'
+        return getattr(self.assigner, 'solver', 'host') in ('device', 'fused')
+
+    def _fused_solver(self):
+        return getattr(self.assigner, 'solver', 'host') == 'fused'
+
+    def _set_loss_fused(self, all_cls, all_box, gts, loss_box_module):
+        """The classification and box terms of all L decoder layers from a ``PaddedGts`` in four launches of ours
+        (train_cfg.assigner.solver = 'fused'): ``det_costs`` -> ``lsa_solve`` -> ``_device_normalisers`` -> ``det_set_loss``,
+        whose backward is the fourth.  Costs, targets, per-element terms and their gradients are what ``_assignment_costs``,
+        ``_targets_from_match`` and ``_losses_from_targets`` state; nothing is copied to the host, so the call can be captured.
+        ``all_cls`` None: the room-layout form (regression cost and L1 term alone, ``loss_box_module`` = ``loss_layout``).
+        -> (loss_cls per layer, loss_bbox per layer).  CPU tensors: the torch formulas of ``solver='device'``."""
+        from .assigner import BBox3DL1Cost, FocalLossCost
+        a = self.assigner
+        if (a is None or not isinstance(a.cls_cost, FocalLossCost) or not isinstance(a.reg_cost, BBox3DL1Cost)
+                or not isinstance(self.loss_cls, losses.FocalLoss) or not isinstance(loss_box_module, losses.L1Loss)):
+            raise NotImplementedError("solver='fused' is built for FocalLossCost + BBox3DL1Cost assigners with FocalLoss + L1Loss")
+        if not all_box.is_cuda:
+            return self._losses_from_targets(all_cls, all_box, *self._targets_device(all_cls, all_box, gts))
+        from ..hipops import AssignmentFlag, det_costs, det_set_loss, lsa_solve
+        nl, bs, nq = all_box.shape[:3]
+        tables = (gts.boxes.float(), gts.labels, gts.counts)
+        c = a.cls_cost
+        flag = AssignmentFlag.of(all_box.device)
+        flag.poll()                                          # a problem of an EARLIER step is reported here
+        with torch.no_grad():
+            cost = det_costs(all_cls, all_box, tables, c.weight, c.alpha, c.gamma, c.eps, a.reg_cost.weight)
+            match = lsa_solve(cost, gts.counts[None].expand(nl, bs), bad=flag.dev)
+            norm = self._device_normalisers((match >= 0).sum((1, 2)), bs * nq)
+        loss_cls, loss_box, _ = det_set_loss(all_cls, all_box, match, tables, self.code_weights, norm,
+                                             (self.loss_cls.loss_weight, loss_box_module.loss_weight), self.loss_cls.alpha,
+                                             self.loss_cls.gamma, bad=flag.dev)
+        flag.mirror(None)
+        return loss_cls.unbind(0), loss_box.unbind(0)
 
     def pad_gts(self, gt_bboxes_list, gt_labels_list, capacity=None):
         """The per-sample gt lists -> ``PaddedGts`` on the head's device, ``capacity`` boxes per sample (default: the

@@ -1337,6 +1337,143 @@ def lsa_solve(cost, ncols, match=None, bad=None):
 
 
 # ------------------------------------------------------------------------------------------
+SET_LOSS_MAX_CLASSES = 64     # ver_det_costs / ver_det_set_loss_*: C (Q and Gcap: LSA_MAX)
+
+
+def _set_loss_operands(what, all_cls, all_box, gts, min_ld):
+    """The operands the three set-loss entry points share, checked: (cls | None, dtype code, box, boxes, labels, counts,
+    (L, B, Q, C, Gcap, box_ld))."""
+    gt_boxes, gt_labels, counts = gts
+    box = _gpu(all_box, 'all_box', torch.float32)
+    if box.dim() != 4 or box.shape[-1] < min_ld:
+        raise ValueError('%s: all_box must be [L, B, Q, >= %d], got %s' % (what, min_ld, tuple(box.shape)))
+    nl, bs, nq, ld = box.shape
+    dev = box.device
+    gt_boxes = _gpu(gt_boxes, 'gts.boxes', torch.float32)
+    if gt_boxes.dim() != 3 or gt_boxes.shape[0] != bs or gt_boxes.shape[2] != 9 or gt_boxes.device != dev:
+        raise ValueError('%s: gts.boxes must be [%d, Gcap, 9] on %s, got %s' % (what, bs, dev, tuple(gt_boxes.shape)))
+    cap = gt_boxes.shape[1]
+    counts = _counts(counts, 'gts.counts', what, bs, dev)
+    if counts is None:
+        raise ValueError('%s: gts.counts is required' % what)
+    ncls, code = 0, 0
+    if all_cls is not None:
+        all_cls = _gpu(all_cls, 'all_cls')
+        if all_cls.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError('%s: all_cls must be float32 or bfloat16, got %s' % (what, all_cls.dtype))
+        if all_cls.dim() != 4 or tuple(all_cls.shape[:3]) != (nl, bs, nq) or all_cls.device != dev:
+            raise ValueError('%s: all_cls must be [%d, %d, %d, C] on %s, got %s' % (what, nl, bs, nq, dev, tuple(all_cls.shape)))
+        ncls, code = all_cls.shape[3], 1 if all_cls.dtype == torch.bfloat16 else 0
+        gt_labels = _gpu(gt_labels, 'gts.labels', torch.int64)
+        if tuple(gt_labels.shape) != (bs, cap) or gt_labels.device != dev:
+            raise ValueError('%s: gts.labels must be int64 [%d, %d] on %s' % (what, bs, cap, dev))
+    else:
+        gt_labels = None
+    if nq > LSA_MAX or cap > LSA_MAX or ncls > SET_LOSS_MAX_CLASSES:
+        raise ValueError('%s: Q=%d Gcap=%d C=%d (at most %d, %d, %d)' % (what, nq, cap, ncls, LSA_MAX, LSA_MAX, SET_LOSS_MAX_CLASSES))
+    return all_cls, code, box, gt_boxes, gt_labels, counts, (nl, bs, nq, ncls, cap, ld)
+
+
+def det_costs(all_cls, all_box, gts, w_cls=1.0, alpha=0.25, gamma=2.0, eps=1e-12, w_reg=1.0):
+    """Matching costs of every (decoder layer, sample) in one launch (ver_det_costs): all_cls fp32 | bf16 [L, B, Q, C] logits
+    or None (the room-layout form: regression cost alone), all_box fp32 [L, B, Q, >= 8] box codes, gts = (boxes fp32
+    [B, Gcap, 9], labels int64 [B, Gcap], counts int32 [B]) as ``PaddedGts`` holds them -> cost fp32 [L, B, Q, Gcap]:
+    ``FocalLossCost`` (w_cls, alpha, gamma, eps) + ``BBox3DL1Cost`` (w_reg) on the normalised box, 0 in the columns past a
+    sample's count, NaN where a valid label lies outside [0, C).  No allocation besides ``cost``, no host synchronisation."""
+    if all_cls is not None and all_cls.dtype not in (torch.float32, torch.bfloat16):
+        all_cls = all_cls.float()
+    cls, code, box, gt_boxes, gt_labels, counts, (nl, bs, nq, ncls, cap, ld) = _set_loss_operands('det_costs', all_cls, all_box.float(), gts, 8)
+    cost = torch.empty(nl, bs, nq, cap, dtype=torch.float32, device=box.device)
+    if cost.numel():
+        _launch('ver_det_costs', lambda: lib().ver_det_costs(
+            _p(cls), code, _p(box), ld, _p(gt_boxes), _p(gt_labels), _p(counts), _p(cost), nl, bs, nq, ncls, cap,
+            float(w_cls), float(alpha), float(gamma), float(eps), float(w_reg), _stream()))
+    return cost
+
+
+def _set_loss_forward(all_cls, all_box, match, gts, code_weights, alpha, gamma, bad):
+    """Launch ver_det_set_loss_forward -> (sums fp32 [2, L], npos int32 [L], the checked operands for the backward)."""
+    what = 'det_set_loss'
+    cls, code, box, gt_boxes, gt_labels, counts, dims = _set_loss_operands(what, all_cls, all_box, gts, 10)
+    nl, bs, nq, ncls, cap, ld = dims
+    dev = box.device
+    match = _gpu(match, 'match', torch.int32)
+    if tuple(match.shape) != (nl, bs, nq) or match.device != dev:
+        raise ValueError('%s: match must be int32 [%d, %d, %d] on %s' % (what, nl, bs, nq, dev))
+    code_weights = _gpu(code_weights.detach(), 'code_weights', torch.float32)
+    if code_weights.numel() < 10 or code_weights.device != dev:
+        raise ValueError('%s: code_weights must hold ten fp32 weights on %s' % (what, dev))
+    if bad is not None and (bad.numel() != 1 or bad.dtype != torch.int32 or bad.device != dev):
+        raise ValueError('%s: bad must be one int32 on %s' % (what, dev))
+    sums = torch.empty(2, nl, dtype=torch.float32, device=dev)
+    npos = torch.empty(nl, dtype=torch.int32, device=dev)
+    if nl:
+        _launch('ver_det_set_loss_forward', lambda: lib().ver_det_set_loss_forward(
+            _p(cls), code, _p(box), ld, _p(match), _p(gt_boxes), _p(gt_labels), _p(counts), _p(code_weights), _p(sums),
+            _p(npos), _p(bad), nl, bs, nq, ncls, cap, float(alpha), float(gamma), _stream()))
+    return sums, npos, (cls, box, match, gt_boxes, gt_labels, counts, code_weights), dims, code
+
+
+def det_set_loss_sums(all_cls, all_box, match, gts, code_weights, alpha=0.25, gamma=2.0, bad=None):
+    """The raw per-layer sums of ``det_set_loss`` without autograd: (sums fp32 [2, L] = focal, code-weighted L1; npos int32
+    [L]), before the weights, the normalisers and ``nan_to_num``.  No caller in the package: it is how the tests read the
+    kernel's own output (bit-reproducibility, the NaN of a flagged layer, which ``det_set_loss`` cleans away)."""
+    return _set_loss_forward(all_cls, all_box, match, gts, code_weights, alpha, gamma, bad)[:2]
+
+
+class DetSetLossFunction(Function):
+    """Focal and L1 terms of all decoder layers from the match (ver_det_set_loss_forward / _backward):
+    -> (loss_cls [L], loss_bbox [L], npos int32 [L]), loss = nan_to_num(loss_weight * sums / norm).  Gradients flow to
+    ``all_cls`` and ``all_box`` only; a layer whose loss nan_to_num cleaned passes none, as torch's nan_to_num does."""
+
+    @staticmethod
+    def forward(ctx, all_cls, all_box, match, gt_boxes, gt_labels, counts, code_weights, norm, loss_weights, alpha, gamma, bad):
+        from .modules.bricks import const_tensor
+        sums, npos, operands, dims, code = _set_loss_forward(all_cls, all_box, match, (gt_boxes, gt_labels, counts), code_weights,
+                                                             alpha, gamma, bad)
+        dev = sums.device
+        norm = _gpu(norm.detach(), 'norm', torch.float32)
+        if tuple(norm.shape) != (2, dims[0]) or norm.device != dev:
+            raise ValueError('det_set_loss: norm must be fp32 [2, %d] on %s' % (dims[0], dev))
+        weights = const_tensor([[float(loss_weights[0])], [float(loss_weights[1])]], dev, torch.float32)
+        raw = weights * sums / norm
+        ctx.save_for_backward(*operands, weights / norm * torch.isfinite(raw))
+        ctx.dims, ctx.code, ctx.alpha, ctx.gamma = dims, code, float(alpha), float(gamma)
+        loss = torch.nan_to_num(raw)
+        ctx.mark_non_differentiable(npos)
+        return loss[0], loss[1], npos
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_cls_loss, grad_box_loss, _grad_npos):
+        cls, box, match, gt_boxes, gt_labels, counts, code_weights, factor = ctx.saved_tensors
+        nl, bs, nq, ncls, cap, ld = ctx.dims
+        grads = [torch.zeros_like(factor[0]) if g is None else g.float() for g in (grad_cls_loss, grad_box_loss)]
+        scale = (torch.stack(grads) * factor).contiguous()
+        grad_cls = None if cls is None else torch.empty_like(cls)
+        grad_box = torch.empty_like(box)
+        if box.numel():
+            _launch('ver_det_set_loss_backward', lambda: lib().ver_det_set_loss_backward(
+                _p(cls), ctx.code, _p(box), ld, _p(match), _p(gt_boxes), _p(gt_labels), _p(counts), _p(code_weights), _p(scale),
+                _p(grad_cls), _p(grad_box), nl, bs, nq, ncls, cap, ctx.alpha, ctx.gamma, _stream()))
+        return (grad_cls, grad_box) + (None,) * 10
+
+
+def det_set_loss(all_cls, all_box, match, gts, code_weights, norm, loss_weights=(1.0, 1.0), alpha=0.25, gamma=2.0, bad=None):
+    """The detection set loss of every decoder layer in one launch each way: all_cls fp32 | bf16 [L, B, Q, C] (None: the
+    layout form, loss_cls is 0), all_box fp32 [L, B, Q, >= 10], match int32 [L, B, Q] (``lsa_solve``), gts = (boxes, labels,
+    counts) as in ``det_costs``, code_weights fp32 [10], norm fp32 [2, L] (the classification and box normalisers per layer),
+    loss_weights = (focal, L1) -> (loss_cls [L], loss_bbox [L], npos int32 [L] = matched rows per layer).
+    ``bad``: an int32 device scalar that gets 1 ORed in when a match or a matched label is out of range (that layer's losses
+    are NaN before nan_to_num, 0 after).  No gradient flows to the ground truth, ``code_weights`` or ``norm``."""
+    gt_boxes, gt_labels, counts = gts
+    if all_cls is not None and all_cls.dtype not in (torch.float32, torch.bfloat16):
+        all_cls = all_cls.float()
+    return DetSetLossFunction.apply(all_cls, all_box.float(), match, gt_boxes, gt_labels, counts, code_weights, norm,
+                                    tuple(loss_weights), alpha, gamma, bad)
+
+
+# ------------------------------------------------------------------------------------------
 DET_MATCH_MAX_BOXES = 1024      # ver_det_match: Pcap, Gcap
 DET_MATCH_MAX_PAIRS = 16384     # ver_det_match: Pcap * Gcap
 DET_MATCH_MAX_THRESHOLDS = 8
