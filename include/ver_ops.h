@@ -741,6 +741,42 @@ int ver_det_set_loss_backward(const void* cls, int cls_dtype, const float* box, 
                               const float* code_weights, const float* scale, void* grad_cls, float* grad_box, int L,
                               int B, int Q, int C, int Gcap, float alpha, float gamma, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Detection decoding on the device (additive to ABI 31; csrc/ver_decode.hip): the reference's NMSFreeCoder.decode
+ * (core/bbox/coders/nms_free_coder.py:9-122: sigmoid, top-k over the flattened [Q * C] scores, label = index % C, query =
+ * index / C, denormalize_bbox of core/bbox/util.py:4-55, centre-range and score masks) for a whole batch in fixed shapes,
+ * with the bottom-centre shift of the head's _to_box_type (head:1466-1471) -- what stands between the decoder's outputs and
+ * ver_det_match.  In place of the torch chain of NMSFreeCoder.decode_padded + head.get_bboxes_padded.
+ *   cls          f32 | bf16 [B, Q, C] class logits of ONE decoder layer (cls_dtype = VER_F32 | VER_BF16), or NULL: the
+ *                layout form below
+ *   box          f32 [B, Q, box_ld] normalised codes (cx, cy, log w, log l, cz, log h, sin, cos[, vx, vy]), row pitch box_ld
+ *   codes        8 or 10 (with the velocity), codes <= box_ld
+ *   center_range HOST f32[6] (x, y, z lower ends, then the upper ends; copied into the kernel arguments)
+ *   out_boxes f32 [B, K, codes - 1], out_scores f32 [B, K], out_labels i32 [B, K], out_valid u8 [B, K], out_query i32 [B, K]
+ *                or NULL: all written in full
+ * SELECTION.  Slot j of sample b holds the j-th entry of the sample's Q * C logits in this order: LOGIT DESCENDING, FLAT INDEX
+ * q * C + c ASCENDING AMONG EQUAL LOGITS.  A NaN logit comes after every number; -0.0 equals +0.0; bf16 logits are widened
+ * to fp32 first (exact).  The fp32 sigmoid 1 / (1 + exp(-x)) is non-decreasing in x, so the K first entries of this order
+ * always are one of the top-k sets `topk` over the sigmoid scores may return, in a score-descending order -- the only one
+ * wherever the K + 1 best scores are distinct.  Where `topk` has a choice (torch promises no order among equal values, and
+ * under bf16 autocast equal logits are the rule) the choice is stated here: the lower flat index.  That also covers
+ * saturation: every logit above about 17 scores exactly 1.0 in fp32, and such slots are still ordered by their logits.
+ * PER SLOT.  idx = the selected flat index:  score = sigmoid(logit) in fp32;  label = idx % C;  query = idx / C (the reference's
+ * bbox_index);  box = (cx, cy, cz, exp(log w), exp(log l), exp(log h), atan2(sin, cos)[, vx, vy]) of that query's codes.
+ *   flags & 1: z = cz - h / 2 (bottom centre);   flags & 2: score_threshold is in force.
+ *   valid = the gravity centre lies inside center_range (six inclusive comparisons, before the z shift)
+ *           AND (flags & 2 == 0 OR score > score_threshold) AND the logit is not a NaN (OUR DEFINITION: torch sorts a NaN
+ *           first).  Boxes, scores and labels are written for the invalid slots too.
+ * LAYOUT FORM (cls == NULL; LayoutCoder.decode, layout_coder.py): K == Q and slot j is query j; scores and labels are written
+ * as 0, valid is the range test alone; cls_dtype and C are not looked at.
+ * One workgroup per sample: a bitonic sort of 64-bit (order word, flat index) keys in LDS, then one thread per slot.
+ * Supported: 0 <= K <= min(Q * C, 1024), Q * C <= 16 384 (VER_EUNSUPPORTED beyond; K > Q * C is VER_EINVAL); B == 0 or K == 0
+ * launches nothing.  One launch, no memset node, no allocation, no host read.
+ */
+int ver_det_decode(const void* cls, int cls_dtype, const float* box, int box_ld, float* out_boxes, float* out_scores,
+                   int32_t* out_labels, uint8_t* out_valid, int32_t* out_query, const float* center_range,
+                   float score_threshold, int flags, int B, int Q, int C, int K, int codes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

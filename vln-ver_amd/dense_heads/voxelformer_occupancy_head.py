@@ -1036,10 +1036,14 @@ class VoxelFormerOccupancyHead(BaseModule):
         metas = img_metas or [None] * len(preds)
         return [[self._to_box_type(p['bboxes'], m), p['scores'], p['labels']] for p, m in zip(preds, metas)]
 
-    def get_bboxes_padded(self, preds_dicts):
+    def get_bboxes_padded(self, preds_dicts, fused=False):
         """``get_bboxes`` in fixed shapes (``bbox_coder.decode_padded``): (boxes [bs, K, box_dim] with bottom-centre z as
         ``_to_box_type`` makes it, scores [bs, K], labels [bs, K], valid uint8 [bs, K]); the slots with ``valid`` set are
-        ``get_bboxes``' boxes in the same order.  Launches only -- what ``DeviceDetMetrics.add`` feeds to the matcher."""
+        ``get_bboxes``' boxes in the same order.  Launches only -- what ``DeviceDetMetrics.add`` feeds to the matcher.
+        ``fused``: one launch (``hipops.det_decode``) that writes the bottom-centre boxes directly; labels are int32 and equal
+        scores are ordered by (query, class) -- the same slots wherever the scores are distinct."""
+        if fused:
+            return self.bbox_coder.decode_padded(preds_dicts, fused=True, bottom_center=True)
         boxes, scores, labels, valid = self.bbox_coder.decode_padded(preds_dicts)
         boxes = boxes.clone()
         boxes[..., 2] = boxes[..., 2] - boxes[..., 5] * 0.5
@@ -1050,6 +1054,17 @@ class VoxelFormerOccupancyHead(BaseModule):
         preds = self.layout_coder.decode(preds_dicts)
         metas = img_metas or [None] * len(preds)
         return [[self._to_box_type(p['layouts'], m)] for p, m in zip(preds, metas)]
+
+    def get_layouts_padded(self, preds_dicts, fused=False):
+        """``get_layouts`` in fixed shapes (``layout_coder.decode_padded``): (layouts [bs, Nq, box_dim] with bottom-centre z,
+        valid uint8 [bs, Nq]); the rows with ``valid`` set are ``get_layouts``' boxes in the same order.  ``fused``: one
+        launch of ours instead of the torch chain."""
+        if fused:
+            return self.layout_coder.decode_padded(preds_dicts, fused=True, bottom_center=True)
+        boxes, valid = self.layout_coder.decode_padded(preds_dicts)
+        boxes = boxes.clone()
+        boxes[..., 2] = boxes[..., 2] - boxes[..., 5] * 0.5
+        return boxes, valid
 
     # ---- Hungarian targets of all decoder layers and samples with ONE device->host round trip
     def _batched_targets(self, all_cls, all_box, gt_boxes, gt_labels):

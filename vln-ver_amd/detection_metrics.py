@@ -7,6 +7,8 @@ Host side (numpy, float64): ``box3d_overlaps_host`` (mmdet3d's ``overlaps(mode='
 the clipped BEV polygon), ``det_match_host`` (the per-image loop of ``eval_det_cls``, indoor_eval.py:54-143),
 ``average_precision``, ``eval_det`` and ``indoor_eval``.  ``DeviceDetMetrics``: the same statistics from records matched
 on the device (``hipops.det_match`` on the boxes of ``head.get_bboxes_padded``), one device->host copy per evaluation.
+``det_decode_host``: the host statement of the fused decoding in front of the matcher (``hipops.det_decode``), with its
+order on equal scores.
 
 Where this differs from the reference by choice: equal scores are ordered by arrival (image, then slot) -- the reference's
 ``np.argsort(-confidence)`` leaves ties in no particular order; AP is float64 (the reference rounds it to float32); a box
@@ -155,6 +157,59 @@ def det_match_host(pred_boxes, pred_labels, pred_scores, pred_valid, gt_boxes, g
     return iou_max, gt_index, tp_bits, dict(npos)
 
 
+def det_decode_host(cls, box, center_range, score_threshold=None, bottom_center=True, k=None):
+    """The host statement of ``ver_det_decode`` (``hipops.det_decode``), float64 numpy: cls [B, Q, C] logits (any float
+    dtype; a torch bf16 tensor is widened exactly) or None (the layout form: every query in order, scores and labels 0),
+    box [B, Q, 8 | 10] normalised codes, ``center_range`` six numbers and ``score_threshold`` (both rounded to float32 first:
+    that is what the kernel and torch's comparison of a float32 tensor with a Python number see).
+    -> (boxes float64 [B, K, 7 | 9], scores float64 [B, K], labels int32, valid uint8, query int32 [B, K]).
+    Slot j is the j-th entry of the flattened [Q * C] logits in (logit descending, flat index ascending) order -- a stable
+    argsort of the negated logits, which leaves a NaN after every number and -0.0 equal to +0.0.  ``valid``: the gravity
+    centre inside the range (inclusive), the score above the threshold, the logit not a NaN."""
+    if hasattr(box, 'detach'):
+        box = box.detach().double().cpu().numpy()
+    box = np.asarray(box, np.float64)
+    if box.ndim != 3 or box.shape[-1] not in (8, 10):
+        raise ValueError('det_decode_host: box must be [B, Q, 8 | 10] normalised codes, got %s' % (box.shape,))
+    bs, nq, codes = box.shape
+    if cls is not None:
+        if hasattr(cls, 'detach'):
+            cls = cls.detach().double().cpu().numpy()
+        logits = np.asarray(cls, np.float64).reshape(bs, nq, -1)
+        ncls = logits.shape[2]
+        flat = logits.reshape(bs, nq * ncls)
+        k = min(nq * ncls, 1024) if k is None else int(k)
+        if not 1 <= k <= nq * ncls:
+            raise ValueError('det_decode_host: k=%d of %d logits' % (k, nq * ncls))
+        index = np.argsort(-flat, axis=1, kind='stable')[:, :k]
+        picked = np.take_along_axis(flat, index, 1)
+        with np.errstate(over='ignore'):
+            scores = 1.0 / (1.0 + np.exp(-picked))
+        labels, query = index % ncls, index // ncls
+        number = ~np.isnan(picked)
+    else:
+        k = nq if k is None else int(k)
+        if k != nq:
+            raise ValueError('det_decode_host: the layout form decodes every query: k=%d, Q=%d' % (k, nq))
+        query = np.tile(np.arange(nq), (bs, 1))
+        labels, scores, number = np.zeros((bs, nq), np.int64), np.zeros((bs, nq)), np.ones((bs, nq), bool)
+    rows = np.take_along_axis(box, query[..., None], 1)
+    with np.errstate(over='ignore', invalid='ignore'):
+        dims = np.exp(rows[..., [2, 3, 5]])
+        yaw = np.arctan2(rows[..., 6], rows[..., 7])
+    centre = rows[..., [0, 1, 4]]
+    rng = np.asarray([float(v) for v in center_range], np.float32).astype(np.float64)
+    with np.errstate(invalid='ignore'):
+        valid = number & (centre >= rng[:3]).all(-1) & (centre <= rng[3:]).all(-1)
+        if score_threshold is not None:
+            valid &= scores > float(np.float32(score_threshold))
+    z = centre[..., 2] - 0.5 * dims[..., 2] if bottom_center else centre[..., 2]
+    parts = [centre[..., 0], centre[..., 1], z, dims[..., 0], dims[..., 1], dims[..., 2], yaw]
+    if codes == 10:
+        parts += [rows[..., 8], rows[..., 9]]
+    return np.stack(parts, -1), scores, labels.astype(np.int32), valid.astype(np.uint8), query.astype(np.int32)
+
+
 def average_precision(recalls, precisions, mode='area'):
     """AP of a recall / precision curve ([n] or [curves, n]) -> float64 [curves].  'area': the area under the precision
     envelope (precision made non-increasing from the right) between recall 0 and 1; '11points': the mean of the best
@@ -275,10 +330,11 @@ class DeviceDetMetrics:
         self.npos = torch.zeros(self.num_classes, dtype=torch.int64, device=device)
         self._parts = []               # in arrival order: device tuples (scores, labels, valid, tp_bits) | host states
 
-    def add(self, head, preds_dicts, gts):
+    def add(self, head, preds_dicts, gts, fused=False):
         """Count one batch: the head's ``preds_dicts`` against ``gts``, a ``PaddedGts`` (``head.pad_gts``) whose boxes are
-        (x, y, z_bottom, dx, dy, dz, yaw[, ...])."""
-        boxes, scores, labels, valid = head.get_bboxes_padded(preds_dicts)
+        (x, y, z_bottom, dx, dy, dz, yaw[, ...]).  ``fused``: decode with ``hipops.det_decode`` -- decoder outputs to
+        records in two launches of ours, equal scores in a stated order (``head.get_bboxes_padded(fused=True)``)."""
+        boxes, scores, labels, valid = head.get_bboxes_padded(preds_dicts, fused=True) if fused else head.get_bboxes_padded(preds_dicts)
         return self.add_padded(boxes, scores, labels, valid, gts)
 
     def add_padded(self, boxes, scores, labels, valid, gts):

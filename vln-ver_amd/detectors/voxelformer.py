@@ -230,12 +230,53 @@ class VoxelFormer(BaseModule):
         metrics.add(head, preds, labels)
         return metrics
 
+    # what ``evaluate_detection(fused=None)`` and ``simple_test_pts`` resolve to.  Off by default: the fused decode orders equal
+    # scores by (query, class), the torch chain in whatever order ``topk`` leaves them -- the same boxes wherever the scores
+    # are distinct (fp32), a stated choice where they are not (bf16 autocast); DESIGN.md 3.10 has the measured launches.
+    fused_detection_decode = False
+
+    def evaluate_detection(self, img_metas, gts, metrics=None, autocast_dtype=None, fused=None):
+        """The detection evaluation of ``simple_test`` followed by ``MP3DDataset.evaluate`` (mp3docc_dataset.py:304-384) for a
+        batch of viewpoints, on the device: head forward, decoding of the last decoder layer, matching against ``gts`` (a
+        ``PaddedGts`` of bottom-centre boxes, ``head.pad_gts``) counted into ``metrics`` (a
+        ``detection_metrics.DeviceDetMetrics``; a new one with the default thresholds when None).  ``autocast_dtype``: 'bf16'
+        runs the head under bf16 autocast.  ``fused``: True decodes with ``hipops.det_decode`` (one launch, equal scores in a
+        stated order), False with the torch chain, None = ``fused_detection_decode``.  -> ``metrics``."""
+        from ..detection_metrics import DeviceDetMetrics
+        head = self.pts_bbox_head
+        if metrics is None:
+            metrics = DeviceDetMetrics(head.num_classes, device=self._device())
+        lowp = {'bf16': torch.bfloat16, 'fp16': torch.float16}.get(autocast_dtype, autocast_dtype)
+        img_feats = self.viewpoint_features(img_metas)
+        with torch.no_grad():
+            with torch.autocast('cuda', dtype=lowp or torch.bfloat16, enabled=lowp is not None and img_feats.is_cuda):
+                outs = head(img_feats, img_metas)
+            if outs.get('all_cls_scores') is None:
+                raise ValueError('evaluate_detection: the head has no detection branch (only_occ)')
+            return metrics.add(head, outs, gts, fused=self.fused_detection_decode if fused is None else fused)
+
+    def _fused_bbox_results(self, outs, img_metas):
+        """``get_bboxes`` + ``bbox3d2result`` from ONE fused decode and ONE device->host copy of the padded tables: the slots
+        are filtered by ``valid`` on the host, ``_to_box_type`` runs after the copy."""
+        head = self.pts_bbox_head
+        boxes, scores, labels, valid = head.bbox_coder.decode_padded(outs, fused=True)
+        table = torch.cat([boxes, scores[..., None], labels[..., None].to(boxes.dtype), valid[..., None].to(boxes.dtype)], -1).cpu()
+        dim = boxes.shape[-1]
+        results = []
+        for rows, meta in zip(table, img_metas or [None] * len(table)):
+            rows = rows[rows[:, dim + 2] != 0]
+            results.append(dict(boxes_3d=head._to_box_type(rows[:, :dim], meta), scores_3d=rows[:, dim].clone(),
+                                labels_3d=rows[:, dim + 1].long()))
+        return results
+
     def simple_test_pts(self, x, img_metas, prev_bev=None, rescale=False):
         """:376-391."""
         outs = self.pts_bbox_head(x, img_metas, prev_bev=prev_bev)
         occ_results = dict(occupancy_preds=outs.get('occupancy_preds', None), flow_preds=None)
         if outs.get('all_cls_scores') is None:                        # only_occ heads have no boxes to decode
             return outs['bev_embed'], None, occ_results
+        if self.fused_detection_decode:
+            return outs['bev_embed'], self._fused_bbox_results(outs, img_metas), occ_results
         bbox_list = self.pts_bbox_head.get_bboxes(outs, img_metas, rescale=rescale)
         bbox_results = [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in bbox_list]
         return outs['bev_embed'], bbox_results, occ_results

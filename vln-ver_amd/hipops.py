@@ -1555,6 +1555,64 @@ def det_match(pred_boxes, pred_labels, pred_scores, pred_valid, gt_boxes, gt_lab
 
 
 # ------------------------------------------------------------------------------------------
+DET_DECODE_MAX_SLOTS = 1024     # ver_det_decode: K
+DET_DECODE_MAX_KEYS = 16384     # ver_det_decode: Q * C
+
+
+def det_decode(cls, box, center_range, score_threshold=None, bottom_center=True, k=None):
+    """NMS-free decoding of one decoder layer in one launch (ver_det_decode): cls fp32 | bf16 [B, Q, C] logits, or None (the
+    room-layout form: every query, in order, no scores); box fp32 [B, Q, 8 | 10] normalised codes (a slice of wider rows is
+    read in place); ``center_range``: six numbers; ``score_threshold``: None or a number; ``bottom_center``: z = cz - h / 2;
+    ``k``: slots per sample (None: min(Q * C, 1024); the layout form always has Q).
+    -> (boxes fp32 [B, K, 7 | 9], scores fp32 [B, K], labels int32 [B, K], valid uint8 [B, K], query int32 [B, K]).  Slot j is
+    the j-th entry in (logit descending, flat index ascending) order, a NaN after every number; ``valid``: centre inside the
+    range, score above the threshold, logit not a NaN.  No host synchronisation."""
+    what = 'det_decode'
+    if not box.is_cuda:
+        raise RuntimeError('box must be a GPU tensor: the VER ops only exist as HIP kernels')
+    if box.dtype != torch.float32:
+        raise TypeError('box must be %s, got %s' % (torch.float32, box.dtype))
+    if box.dim() != 3 or box.shape[-1] not in (8, 10) or box.shape[1] < 1:
+        raise ValueError('%s: box must be [B, Q >= 1, 8 | 10] normalised codes, got %s' % (what, tuple(box.shape)))
+    bs, nq, codes = box.shape
+    if not (box.stride(2) == 1 and box.stride(1) >= codes and (bs <= 1 or box.stride(0) == nq * box.stride(1))):
+        box = box.contiguous()
+    ld, dev = box.stride(1), box.device
+    ncls, code = 0, 0
+    if cls is not None:
+        cls = _gpu(cls, 'cls')
+        if cls.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError('%s: cls must be float32 or bfloat16, got %s' % (what, cls.dtype))
+        if cls.dim() != 3 or tuple(cls.shape[:2]) != (bs, nq) or cls.shape[2] < 1 or cls.device != dev:
+            raise ValueError('%s: cls must be [%d, %d, C >= 1] on %s, got %s on %s' % (what, bs, nq, dev, tuple(cls.shape), cls.device))
+        ncls, code = cls.shape[2], 1 if cls.dtype == torch.bfloat16 else 0
+        keys = nq * ncls
+        k = min(keys, DET_DECODE_MAX_SLOTS) if k is None else int(k)
+    else:
+        keys = nq
+        k = nq if k is None else int(k)
+        if k != nq:
+            raise ValueError('%s: the layout form decodes every query: k=%d, Q=%d' % (what, k, nq))
+    if not 1 <= k <= min(keys, DET_DECODE_MAX_SLOTS) or keys > DET_DECODE_MAX_KEYS:
+        raise ValueError('%s: k=%d Q*C=%d (1 <= k <= min(Q*C, %d), Q*C <= %d)' % (what, k, keys, DET_DECODE_MAX_SLOTS, DET_DECODE_MAX_KEYS))
+    rng = [float(v) for v in center_range]
+    if len(rng) != 6:
+        raise ValueError('%s: center_range holds %d numbers (6)' % (what, len(rng)))
+    flags = (1 if bottom_center else 0) | (2 if score_threshold is not None else 0)
+    boxes = torch.empty(bs, k, codes - 1, dtype=torch.float32, device=dev)
+    scores = torch.empty(bs, k, dtype=torch.float32, device=dev)
+    labels = torch.empty(bs, k, dtype=torch.int32, device=dev)
+    valid = torch.empty(bs, k, dtype=torch.uint8, device=dev)
+    query = torch.empty(bs, k, dtype=torch.int32, device=dev)
+    if bs:
+        host_rng = (ctypes.c_float * 6)(*rng)
+        _launch('ver_det_decode', lambda: lib().ver_det_decode(
+            _p(cls), code, _p(box), ld, _p(boxes), _p(scores), _p(labels), _p(valid), _p(query), host_rng,
+            float(score_threshold or 0.0), flags, bs, nq, ncls, k, codes, _stream()))
+    return boxes, scores, labels, valid, query
+
+
+# ------------------------------------------------------------------------------------------
 def wgrad_tn_supported(a, g):
     """Shapes / strides ``wgrad_tn`` takes: bf16 GPU matrices, unit column stride, 16-byte aligned rows."""
     return (a.is_cuda and g.is_cuda and a.dtype == torch.bfloat16 and g.dtype == torch.bfloat16 and a.dim() == 2
