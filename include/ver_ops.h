@@ -342,6 +342,27 @@ int ver_focal_loss_forward_grad_u8(const void* logits, const uint8_t* target, fl
                                    float gamma, float alpha, int dtype, int32_t* bad_labels, void* stream);
 int ver_focal_loss_backward(const void* logits, const int64_t* target, const float* scale, void* grad,
                             long N, int C, float gamma, float alpha, int dtype, void* stream);
+/*   class weights (the `_cw` twins; head:1417-1425 `weight=weights[gt_occupancy]` of loss_only_occupancy -> mmdet's
+ *             `loss * weight.view(-1, 1)`): class_weight f32 [C + 1] on the device, one factor per label value in [0, C]
+ *             (index C = the empty / background label); every element of row n is multiplied by class_weight[target[n]]:
+ *               forward sum = sum_n class_weight[t_n] * sum_c loss[n, c]
+ *               gradient    = class_weight[t_n] * d loss[n, c] / d logits[n, c]   (no gradient to the table)
+ *             The caller's avg_factor stays the UNWEIGHTED count of occupied voxels, as in the reference.  A label
+ *             outside [0, C] never indexes the table (factor 0); the sum is NaN and *bad_labels is raised as above.
+ *             Same arguments and checks as the twins, plus C + 1 <= 256 (VER_EUNSUPPORTED otherwise: the table is
+ *             staged on chip) and class_weight != NULL when N > 0 (VER_EINVAL).  A table of ones gives the forward
+ *             twins' partials and gradients bit for bit.  N == 0: VER_OK, nothing is launched
+ *             (ver_focal_loss_forward_cw then leaves `partial` as the caller zero-filled it). */
+int ver_focal_loss_forward_cw(const void* logits, const int64_t* target, const float* class_weight, float* partial,
+                              long N, int C, float gamma, float alpha, int dtype, int32_t* bad_labels, void* stream);
+int ver_focal_loss_forward_grad_cw(const void* logits, const int64_t* target, const float* class_weight, float* partial,
+                                   void* grad, long N, int C, float gamma, float alpha, int dtype, int32_t* bad_labels,
+                                   void* stream);
+int ver_focal_loss_forward_grad_u8_cw(const void* logits, const uint8_t* target, const float* class_weight, float* partial,
+                                      void* grad, long N, int C, float gamma, float alpha, int dtype, int32_t* bad_labels,
+                                      void* stream);
+int ver_focal_loss_backward_cw(const void* logits, const int64_t* target, const float* class_weight, const float* scale,
+                               void* grad, long N, int C, float gamma, float alpha, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * y = LayerNorm(residual + dropout(a)): how both branches of the reference's VoxelFormerLayer end

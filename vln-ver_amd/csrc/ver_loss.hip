@@ -15,6 +15,17 @@
 // (fp32) loads.  A target outside [0, C] makes the forward sum NaN (the reference raises in F.one_hot).
 // The sum is reduced per workgroup into `partial[blockIdx]` (the caller adds the
 // <= 4096 partials: deterministic, no float atomics).
+//
+// Class weights (the `_cw` entries; head:1417-1425, `weight=weights[gt_occupancy]` -> mmdet's `loss * weight.view(-1, 1)`):
+// every element of row n is multiplied by class_weight[target[n]], class_weight f32 [C + 1].  The table is staged in an
+// LDS COPY filled at block start (C + 1 <= 256 floats: one per thread, one barrier; at most 4096 blocks fill it once each) and
+// looked up once per 16-byte vector next to the label -- a dependent global read would put a second memory latency behind
+// the label's in a pass that is latency bound already, the LDS read is ~64 cycles and free of bank conflicts at the occupancy
+// head's size (lanes with one label read one address; 17 entries lie in 17 banks).  The factor is folded into the two constants of the
+// term, alpha w and (1 - alpha) w: two multiplies per vector, and loss and gradient both carry it.  A label outside [0, C]
+// never indexes the table (its factor is 0; the sum is NaN and the flag is raised as without weights).  The weighted
+// kernels are further instantiations of the two templates below whose trailing parameter pack holds the table pointer: with
+// an empty pack the kernels have the argument list -- and the instruction streams -- they had before there were weights.
 #include "ver_common.h"
 
 namespace {
@@ -24,8 +35,9 @@ struct Term {
 
 // FAST (bf16 logits, 1e-2 tolerance): log(1+e) through the hardware log instead of the ~60-instruction
 // log1pf -- its 1e-7 absolute error only shows where exp(-|x|) < 1e-5, i.e. |x| > 11.5.
-template <bool G2, bool FAST>
-__device__ __forceinline__ Term focal_term(float x, bool pos, float gamma, float alpha) {
+// CW: `alpha` and `beta` are the row's alpha w and (1 - alpha) w
+template <bool G2, bool FAST, bool CW = false>
+__device__ __forceinline__ Term focal_term(float x, bool pos, float gamma, float alpha, float beta = 0.0f) {
     if constexpr (FAST && G2) {
         // the bf16 / gamma = 2 form of the step, ~28 instructions per element: with s = 1 + exp(-|x|), p and q = 1 - p are
         // 1/s and e/s in the order the sign of x says (no subtraction), softplus(-x) = softplus(x) - x, and both branches are
@@ -38,7 +50,7 @@ __device__ __forceinline__ Term focal_term(float x, bool pos, float gamma, float
         const float sp_pos = fmaxf(x, 0.0f) + 0.6931471805599453f * __builtin_amdgcn_logf(s1);
         const float u = pos ? qq : pp, w = pos ? pp : qq;
         const float sp = pos ? sp_pos - x : sp_pos;
-        const float cu2 = (pos ? alpha : 1.0f - alpha) * (u * u);
+        const float cu2 = (pos ? alpha : (CW ? beta : 1.0f - alpha)) * (u * u);
         Term t;
         t.loss = cu2 * sp;
         const float tt = __builtin_fmaf(w + w, sp, u);
@@ -63,8 +75,8 @@ __device__ __forceinline__ Term focal_term(float x, bool pos, float gamma, float
         t.grad = alpha * m * (-gamma * p * sp_neg - q);
     } else {
         const float m = G2 ? p * p : powf(p, gamma);
-        t.loss = (1.0f - alpha) * m * sp_pos;
-        t.grad = (1.0f - alpha) * m * (p + gamma * q * sp_pos);
+        t.loss = (CW ? beta : 1.0f - alpha) * m * sp_pos;
+        t.grad = (CW ? beta : 1.0f - alpha) * m * (p + gamma * q * sp_pos);
     }
     return t;
 }
@@ -100,18 +112,34 @@ __device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
     const f32x2 v = {lo, hi};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
 }
+
+// the class-weight table of a kernel's trailing pack (none: the unweighted instantiation)
+__device__ __forceinline__ const float* table_of() { return nullptr; }
+__device__ __forceinline__ const float* table_of(const float* class_weight) { return class_weight; }
+// block start: class_weight[0 .. C] -> LDS (C + 1 <= 256 = the block)
+__device__ __forceinline__ void stage_table(float (&tab)[256], const float* class_weight, int classes) {
+    if ((int)threadIdx.x <= classes) tab[threadIdx.x] = class_weight[threadIdx.x];
+    __syncthreads();
+}
+// the row's factor; a label outside [0, C] does not index the table
+__device__ __forceinline__ float weight_of(const float (&tab)[256], int64_t t64, int classes) {
+    return (uint64_t)t64 <= (uint64_t)classes ? tab[(int)t64] : 0.0f;
+}
 }  // namespace
 
 // WG (ver_focal_loss_forward_grad): the same pass also writes the UNSCALED gradient d loss[n,c] / d logits[n,c] (in the
 // logits' dtype) to `grad`, which may be the logits buffer itself (a thread reads its eight logits before it writes their
 // gradients): a training step that needs the loss value and the gradient, not the logits, then has no separate backward
 // pass over the [N, C] tensor -- the consumer applies the scalar d(total) / d(loss sum) when it reads the gradient.
-template <bool BF16, bool G2, bool WG = false, typename LT = int64_t>
+template <bool BF16, bool G2, bool WG = false, typename LT = int64_t, typename... CW>
 __global__ __launch_bounds__(256) void k_focal_fwd(const void* logits, const LT* __restrict__ target,
                                                    float* __restrict__ partial, long nvec, int vec_per_row,
                                                    float gamma, float alpha, int* __restrict__ bad_labels,
-                                                   void* grad = nullptr, int row_shift = -1) {
+                                                   void* grad = nullptr, int row_shift = -1, CW... class_weight) {
+    constexpr bool W = sizeof...(CW) != 0;
     __shared__ float red[4];
+    __shared__ float wtab[W ? 256 : 1];
+    if constexpr (W) stage_table(wtab, table_of(class_weight...), vec_per_row * 8);
     float acc = 0.0f;
     bool bad = false;
     // row of a 16-byte vector: a shift when the row holds a power of two of them (16 classes: two) -- the general form is a
@@ -121,9 +149,17 @@ __global__ __launch_bounds__(256) void k_focal_fwd(const void* logits, const LT*
         const int c0 = (int)(v - row * vec_per_row) * 8;
         const int tgt = (int)t64;
         float g[8];
+        float ca = 0.0f, cb = 0.0f;                        // the row's alpha w and (1 - alpha) w
+        if constexpr (W) {
+            const float w = weight_of(wtab, t64, vec_per_row * 8);
+            ca = alpha * w;
+            cb = (1.0f - alpha) * w;
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const Term t = focal_term<G2, BF16>(x[j], tgt == c0 + j, gamma, alpha);
+            // (the unweighted call is spelled as it was before there were weights: that keeps its instruction stream)
+            const Term t = W ? focal_term<G2, BF16, true>(x[j], tgt == c0 + j, gamma, ca, cb)
+                             : focal_term<G2, BF16>(x[j], tgt == c0 + j, gamma, alpha);
             acc += t.loss;
             g[j] = t.grad;
         }
@@ -180,19 +216,33 @@ __global__ __launch_bounds__(256) void k_focal_fwd(const void* logits, const LT*
     if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-template <bool BF16, bool G2>
+template <bool BF16, bool G2, typename... CW>
 __global__ __launch_bounds__(256) void k_focal_bwd(const void* __restrict__ logits, const int64_t* __restrict__ target,
                                                    const float* __restrict__ scale, void* __restrict__ grad, long nvec,
-                                                   int vec_per_row, float gamma, float alpha, int row_shift) {
+                                                   int vec_per_row, float gamma, float alpha, int row_shift,
+                                                   CW... class_weight) {
+    constexpr bool W = sizeof...(CW) != 0;
+    __shared__ float wtab[W ? 256 : 1];
+    if constexpr (W) stage_table(wtab, table_of(class_weight...), vec_per_row * 8);
     const float s = scale[0];
     for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += (long)gridDim.x * 256) {
         const long row = row_shift >= 0 ? (v >> row_shift) : v / vec_per_row;
         const int c0 = (int)(v - row * vec_per_row) * 8;
-        const int tgt = (int)target[row];
+        const int64_t t64 = target[row];
+        const int tgt = (int)t64;
         float x[8], g[8];
         load_x8<BF16>(logits, v, x);
+        float ca = 0.0f, cb = 0.0f;                        // the row's alpha w and (1 - alpha) w
+        if constexpr (W) {
+            const float w = weight_of(wtab, t64, vec_per_row * 8);
+            ca = alpha * w;
+            cb = (1.0f - alpha) * w;
+        }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) g[j] = s * focal_term<G2, BF16>(x[j], tgt == c0 + j, gamma, alpha).grad;
+        for (int j = 0; j < 8; ++j) {
+            g[j] = s * (W ? focal_term<G2, BF16, true>(x[j], tgt == c0 + j, gamma, ca, cb)
+                          : focal_term<G2, BF16>(x[j], tgt == c0 + j, gamma, alpha)).grad;
+        }
         if (BF16) {
             uint4 t;
             t.x = pack_bf16(g[0], g[1]);
@@ -322,3 +372,104 @@ extern "C" int ver_focal_loss_backward(const void* logits, const int64_t* target
 #undef VER_FOCAL_BWD
     return ver_check_launch("ver_focal_loss_backward");
 }
+
+// ---- class-weighted twins: the same kernels with the table pointer in their trailing pack
+namespace {
+int check_table(const char* who, const float* class_weight, long N, int C) {
+    VER_REQUIRE(C + 1 <= 256, VER_EUNSUPPORTED, "%s: a table of %d class weights does not fit the staged copy (256)", who, C + 1);
+    VER_REQUIRE(N == 0 || class_weight, VER_EINVAL, "%s: null class_weight", who);
+    return VER_OK;
+}
+}  // namespace
+
+#define VER_FOCAL_CW(KERNEL, ...)                                                                    \
+    do {                                                                                             \
+        if (dtype == VER_BF16) {                                                                     \
+            if (g2) hipLaunchKernelGGL((KERNEL(true, true)), dim3(blocks), dim3(256), 0, st, __VA_ARGS__);  \
+            else hipLaunchKernelGGL((KERNEL(true, false)), dim3(blocks), dim3(256), 0, st, __VA_ARGS__);    \
+        } else {                                                                                     \
+            if (g2) hipLaunchKernelGGL((KERNEL(false, true)), dim3(blocks), dim3(256), 0, st, __VA_ARGS__); \
+            else hipLaunchKernelGGL((KERNEL(false, false)), dim3(blocks), dim3(256), 0, st, __VA_ARGS__);   \
+        }                                                                                            \
+    } while (0)
+
+extern "C" int ver_focal_loss_forward_cw(const void* logits, const int64_t* target, const float* class_weight, float* partial,
+                                         long N, int C, float gamma, float alpha, int dtype, int32_t* bad_labels, void* stream) {
+    int rc = check_focal("ver_focal_loss_forward_cw", logits, target, N, C, dtype);
+    if (rc) return rc;
+    rc = check_table("ver_focal_loss_forward_cw", class_weight, N, C);
+    if (rc) return rc;
+    VER_REQUIRE(partial, VER_EINVAL, "ver_focal_loss_forward_cw: null partial-sum buffer");
+    if (N == 0) return VER_OK;                 // no rows, no table to stage: nothing is launched, `partial` is not written
+    const int blocks = ver_focal_loss_blocks(N, C);
+    const long nvec = N * (long)(C / 8);
+    hipStream_t st = (hipStream_t)stream;
+    const bool g2 = gamma == 2.0f;
+#define VER_K(BF, G2) k_focal_fwd<BF, G2, false, int64_t, const float*>
+    VER_FOCAL_CW(VER_K, logits, target, partial, nvec, C / 8, gamma, alpha, bad_labels, (void*)nullptr, row_shift_of(C / 8),
+                 class_weight);
+#undef VER_K
+    return ver_check_launch("ver_focal_loss_forward_cw");
+}
+
+extern "C" int ver_focal_loss_forward_grad_cw(const void* logits, const int64_t* target, const float* class_weight,
+                                              float* partial, void* grad, long N, int C, float gamma, float alpha, int dtype,
+                                              int32_t* bad_labels, void* stream) {
+    int rc = check_focal("ver_focal_loss_forward_grad_cw", logits, target, N, C, dtype);
+    if (rc) return rc;
+    rc = check_table("ver_focal_loss_forward_grad_cw", class_weight, N, C);
+    if (rc) return rc;
+    VER_REQUIRE(partial, VER_EINVAL, "ver_focal_loss_forward_grad_cw: null partial-sum buffer");
+    if (N == 0) return VER_OK;
+    VER_REQUIRE(grad && ((uintptr_t)grad & 15) == 0, VER_EINVAL, "ver_focal_loss_forward_grad_cw: grad must be a 16-byte aligned buffer");
+    const int blocks = ver_focal_loss_blocks(N, C);
+    const long nvec = N * (long)(C / 8);
+    hipStream_t st = (hipStream_t)stream;
+    const bool g2 = gamma == 2.0f;
+#define VER_K(BF, G2) k_focal_fwd<BF, G2, true, int64_t, const float*>
+    VER_FOCAL_CW(VER_K, logits, target, partial, nvec, C / 8, gamma, alpha, bad_labels, grad, row_shift_of(C / 8), class_weight);
+#undef VER_K
+    return ver_check_launch("ver_focal_loss_forward_grad_cw");
+}
+
+extern "C" int ver_focal_loss_forward_grad_u8_cw(const void* logits, const uint8_t* target, const float* class_weight,
+                                                 float* partial, void* grad, long N, int C, float gamma, float alpha, int dtype,
+                                                 int32_t* bad_labels, void* stream) {
+    int rc = check_focal("ver_focal_loss_forward_grad_u8_cw", logits, reinterpret_cast<const int64_t*>(target), N, C, dtype);
+    if (rc) return rc;
+    // (C + 1 <= 256 with C % 8 == 0 leaves C <= 248: the labels fit their bytes)
+    rc = check_table("ver_focal_loss_forward_grad_u8_cw", class_weight, N, C);
+    if (rc) return rc;
+    VER_REQUIRE(partial, VER_EINVAL, "ver_focal_loss_forward_grad_u8_cw: null partial-sum buffer");
+    if (N == 0) return VER_OK;
+    VER_REQUIRE(grad && ((uintptr_t)grad & 15) == 0, VER_EINVAL, "ver_focal_loss_forward_grad_u8_cw: grad must be a 16-byte aligned buffer");
+    const int blocks = ver_focal_loss_blocks(N, C);
+    const long nvec = N * (long)(C / 8);
+    hipStream_t st = (hipStream_t)stream;
+    const bool g2 = gamma == 2.0f;
+#define VER_K(BF, G2) k_focal_fwd<BF, G2, true, uint8_t, const float*>
+    VER_FOCAL_CW(VER_K, logits, target, partial, nvec, C / 8, gamma, alpha, bad_labels, grad, row_shift_of(C / 8), class_weight);
+#undef VER_K
+    return ver_check_launch("ver_focal_loss_forward_grad_u8_cw");
+}
+
+extern "C" int ver_focal_loss_backward_cw(const void* logits, const int64_t* target, const float* class_weight,
+                                          const float* scale, void* grad, long N, int C, float gamma, float alpha, int dtype,
+                                          void* stream) {
+    int rc = check_focal("ver_focal_loss_backward_cw", logits, target, N, C, dtype);
+    if (rc) return rc;
+    rc = check_table("ver_focal_loss_backward_cw", class_weight, N, C);
+    if (rc) return rc;
+    if (N == 0) return VER_OK;
+    VER_REQUIRE(scale && grad, VER_EINVAL, "ver_focal_loss_backward_cw: null pointer argument");
+    VER_REQUIRE(((uintptr_t)grad & 15) == 0, VER_EINVAL, "ver_focal_loss_backward_cw: grad must be 16-byte aligned");
+    const int blocks = ver_focal_loss_blocks(N, C);
+    const long nvec = N * (long)(C / 8);
+    hipStream_t st = (hipStream_t)stream;
+    const bool g2 = gamma == 2.0f;
+#define VER_K(BF, G2) k_focal_bwd<BF, G2, const float*>
+    VER_FOCAL_CW(VER_K, logits, target, scale, grad, nvec, C / 8, gamma, alpha, row_shift_of(C / 8), class_weight);
+#undef VER_K
+    return ver_check_launch("ver_focal_loss_backward_cw");
+}
+#undef VER_FOCAL_CW

@@ -57,7 +57,10 @@ class FocalLoss(nn.Module):
         self.reduction, self.loss_weight = reduction, loss_weight
         self._labels_checked = False
 
-    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None):
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, class_weight=None):
+        """``class_weight`` (extension of mmdet's signature): fp32 [C + 1], one factor per label value in [0, C]; row n is
+        multiplied by class_weight[target[n]] -- the reference's ``weight=weights[gt_occupancy]`` (head:1417-1425) without
+        the [N] tensor.  ``avg_factor`` is the caller's and stays unweighted."""
         reduction = reduction_override if reduction_override else self.reduction
         if (pred.is_cuda and weight is None and reduction == 'mean' and avg_factor is not None
                 and pred.dim() == 2 and pred.size(1) % 8 == 0 and pred.size(0) >= 4096
@@ -71,7 +74,18 @@ class FocalLoss(nn.Module):
             # the first fused call of a module only (VER_FOCAL_CHECK=2: every call, 0: never).
             self.check_label_range(target, pred.size(1))
             from ..hipops import sigmoid_focal_loss_sum
-            return self.loss_weight * (sigmoid_focal_loss_sum(pred, target, self.gamma, self.alpha) / avg_factor)
+            return self.loss_weight * (sigmoid_focal_loss_sum(pred, target, self.gamma, self.alpha, class_weight)
+                                       / avg_factor)
+        if class_weight is not None:
+            # the lookup uses a clamped index: a label outside [0, C] raises in F.one_hot below, as without weights, and
+            # never becomes an out-of-bounds index
+            if tuple(class_weight.shape) != (pred.size(1) + 1,):
+                raise ValueError('class_weight must be [%d], got %s' % (pred.size(1) + 1, tuple(class_weight.shape)))
+            row = class_weight.detach().to(pred.device)[target.clamp(0, pred.size(1))].type_as(pred)
+            if weight is None:
+                weight = row
+            else:
+                weight = weight * (row.view(-1, 1) if weight.dim() == 2 else row)
         return self.loss_weight * sigmoid_focal_loss(pred, target, weight, self.gamma, self.alpha,
                                                      reduction, avg_factor)
 

@@ -246,15 +246,43 @@ class VoxelFormerOccupancyHead(BaseModule):
             return full_volume(e, b)
         return self.up_sample(x)
 
-    def occupancy_loss_from_volume(self, voxel_embed, gt_occupancy):
-        """``occupancy_loss(occupancy_from_volume(voxel_embed), gt_occupancy)`` for training steps that need the loss
+    def class_weight_table(self, class_weights, device):
+        """The class-weight argument of the occupancy losses -> fp32 [occupancy_classes + 1] on ``device``, or None.
+        ``class_weights``: None (unweighted), True (``self.occ_weights``; unweighted when that is None), a sequence of
+        numbers or a tensor.  A sequence is validated on the host -- exactly occupancy_classes + 1 finite numbers -- and
+        becomes a constant that is created once per (values, device): no host -> device copy per step (the reference makes
+        one, head:1419), so a step with weights can be captured after one eager warm-up; reassigning ``self.occ_weights``
+        gives other values and with them another table.  It is no parameter and no buffer: the state dict is the
+        reference's.  A tensor is the caller's own (it may overwrite it in place between steps)."""
+        if class_weights is True:
+            class_weights = self.occ_weights
+        if class_weights is None or class_weights is False:
+            return None
+        n = self.occupancy_classes + 1
+        if torch.is_tensor(class_weights):
+            if tuple(class_weights.shape) != (n,):
+                raise ValueError('occupancy class weights must be [%d] (one per label in [0, %d]), got %s'
+                                 % (n, n - 1, tuple(class_weights.shape)))
+            return class_weights.detach().to(device=device, dtype=torch.float32)
+        try:
+            values = tuple(float(v) for v in class_weights)
+        except TypeError:
+            raise ValueError('occ_weights must be a sequence of %d numbers, got %r' % (n, class_weights)) from None
+        if len(values) != n or not all(math.isfinite(v) for v in values):
+            raise ValueError('occ_weights must be %d finite numbers (one per label in [0, %d], the last for the empty '
+                             'label), got %r' % (n, n - 1, class_weights))
+        return const_tensor(values, device, torch.float32)
+
+    def occupancy_loss_from_volume(self, voxel_embed, gt_occupancy, class_weights=None):
+        """``occupancy_loss(occupancy_from_volume(voxel_embed), gt_occupancy, class_weights)`` for training steps that need the loss
         and not the logits: on the lattice path the logits stay in the row order the GEMMs left them in and the
         TARGETS are brought into that order instead (an int64 per voxel instead of 16 logits, and no permutation in
         the backward pass).  The loss is a sum over (logit row, target) pairs -- the same pairs, the same value."""
-        res = self.occupancy_from_volume(voxel_embed, rows_only=True, loss_targets=gt_occupancy)
+        table = self.class_weight_table(class_weights, voxel_embed.device)
+        res = self.occupancy_from_volume(voxel_embed, rows_only=True, loss_targets=gt_occupancy, loss_class_weight=table)
         if torch.is_tensor(res) and res.dim() == 0:
             return res                              # the fused MLP + focal-loss path evaluated the loss itself
-        return self.occupancy_loss(res, gt_occupancy)
+        return self.occupancy_loss(res, gt_occupancy, table)
 
     fuse_occ_mlp_loss = True          # (class switch for tests / A-B runs: 0 = logits, then the loss as a separate op)
 
@@ -313,7 +341,7 @@ class VoxelFormerOccupancyHead(BaseModule):
                 return res[0], res[1], fold
         return None
 
-    def occupancy_from_volume(self, voxel_embed, rows_only=False, loss_targets=None):
+    def occupancy_from_volume(self, voxel_embed, rows_only=False, loss_targets=None, loss_class_weight=None):
         """voxel_embed [bs, Nq, C] (per-sample contiguous Nq*C buffer = the reference's
         ``bev_embed`` at bs=1) -> occupancy logits [bs, X*Y*Z, classes]   (head:554-580).
         ``rows_only`` (lattice path): return ``(logits [bs*X*Y, Z, classes] in GEMM row order, plan, bs)`` instead."""
@@ -331,7 +359,7 @@ class VoxelFormerOccupancyHead(BaseModule):
                 # training loss only: the MLP kernel's logits go straight into the focal-loss pass, which leaves
                 # the unscaled gradient in their place; the MLP backward reads it with the loss's scalar factor
                 # (hipops.OccMLPFocalLossFunction) -- no focal backward pass over the [N, 16] tensor
-                return self._occ_mlp_focal_loss(rows.view(-1, self.occ_dims), loss_targets, plan, bs)
+                return self._occ_mlp_focal_loss(rows.view(-1, self.occ_dims), loss_targets, plan, bs, loss_class_weight)
             logits = self._occ_mlp(rows.view(rows.shape[0], self.occ_zdim, self.occ_dims), first_folded=fold)
             if rows_only:
                 return logits, plan, bs
@@ -382,9 +410,10 @@ class VoxelFormerOccupancyHead(BaseModule):
             x.dtype == torch.bfloat16 or (torch.is_autocast_enabled('cuda') and
                                           torch.get_autocast_dtype('cuda') == torch.bfloat16))
 
-    def _occ_mlp_focal_loss(self, x, gt_occupancy, plan, bs):
+    def _occ_mlp_focal_loss(self, x, gt_occupancy, plan, bs, class_weight=None):
         """``occupancy_loss`` of the fused bf16 path with a folded (and centred) first Linear, evaluated as ONE autograd
-        Function: x [N, 128] rows in GEMM order, gt_occupancy in the reference's (Z, X, Y) voxel order."""
+        Function: x [N, 128] rows in GEMM order, gt_occupancy in the reference's (Z, X, Y) voxel order.  ``class_weight``:
+        the table of ``class_weight_table`` -- indexed by label VALUE, so the row permutation of the labels leaves it alone."""
         from ..hipops import occ_mlp_focal_loss_sum
         _, n1, _, l2, n2, _, l3 = list(self.occ_branches)
         lo = self.loss_occupancy
@@ -410,7 +439,8 @@ class VoxelFormerOccupancyHead(BaseModule):
         with torch.autocast('cuda', enabled=False):
             w2c, b2c = self._centered(l2.weight.float(), l2.bias.float())
             s = occ_mlp_focal_loss_sum(x.to(torch.bfloat16), n1.weight, n1.bias, w2c, b2c, n2.weight, n2.bias,
-                                       l3.weight, l3.bias, gt, n1.eps, lo.gamma, lo.alpha, centered=True)
+                                       l3.weight, l3.bias, gt, n1.eps, lo.gamma, lo.alpha, centered=True,
+                                       class_weight=class_weight)
         return torch.nan_to_num(lo.loss_weight * (s / avg))
 
     def _occ_mlp(self, x, first_folded=False):
@@ -609,10 +639,12 @@ class VoxelFormerOccupancyHead(BaseModule):
             occ = occ.permute(0, 3, 1, 2, 4)
         return self._occ_mlp(occ.reshape(bs, -1, self.occ_dims))
 
-    def occupancy_loss(self, occupancy_preds, gt_occupancy):
+    def occupancy_loss(self, occupancy_preds, gt_occupancy, class_weights=None):
         """Occupancy term of ``loss_single`` (head:977-989): sigmoid focal loss over
         [N, classes] logits with integer targets in [0, classes] (``classes`` = empty voxel),
-        normalised by the number of occupied voxels, NaN-guarded."""
+        normalised by the number of occupied voxels, NaN-guarded.  ``class_weights`` (``class_weight_table``): every row
+        times the factor of its label, as ``loss_only_occupancy`` does with ``occ_weights`` (head:1417-1425); the
+        normaliser stays the unweighted count."""
         if isinstance(occupancy_preds, tuple):                         # (logits in GEMM row order, plan, bs)
             occupancy_preds, plan, bs = occupancy_preds               # [bs*X*Y, Z, classes], group-major rows
             gt = gt_occupancy.reshape(bs, self.occ_zdim, plan.rows).permute(0, 2, 1)   # (Z, X, Y) order -> [bs, X*Y, Z]
@@ -622,7 +654,10 @@ class VoxelFormerOccupancyHead(BaseModule):
             preds = preds.float()
         gt = gt_occupancy.reshape(-1)
         avg = (gt < self.occupancy_classes).sum() * 1.0
-        return torch.nan_to_num(self.loss_occupancy(preds, gt, avg_factor=avg))
+        table = self.class_weight_table(class_weights, preds.device)
+        if table is None:
+            return torch.nan_to_num(self.loss_occupancy(preds, gt, avg_factor=avg))
+        return torch.nan_to_num(self.loss_occupancy(preds, gt, avg_factor=avg, class_weight=table))
 
     # ------------------------------------------------------------------ detection losses
     def _get_target_single(self, cls_score, bbox_pred, gt_labels, gt_bboxes):
@@ -893,8 +928,10 @@ class VoxelFormerOccupancyHead(BaseModule):
         return dict(occupancy_preds=self.occupancy_pairs_from_classes(classes), flow_preds=None)
 
     def loss_only_occupancy(self, gt_bboxes_list, gt_labels_list, gt_occupancy, preds_dicts):
-        """``only_occ`` detectors (head:1387-1447): the occupancy focal loss alone, plus the zero ``loss_flow``."""
-        lo = self.occupancy_loss(preds_dicts['occupancy_preds'], gt_occupancy)
+        """``only_occ`` detectors (head:1387-1447): the occupancy focal loss alone, weighted per class by ``occ_weights``
+        when the config sets them (head:1417-1425; ``loss`` / ``loss_addlayout`` do not read them, there as here), plus
+        the zero ``loss_flow``."""
+        lo = self.occupancy_loss(preds_dicts['occupancy_preds'], gt_occupancy, class_weights=True)
         return dict(loss_occupancy=lo, loss_flow=torch.zeros_like(lo))
 
     def loss_only_detection(self, gt_bboxes_list, gt_labels_list, preds_dicts):

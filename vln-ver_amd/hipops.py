@@ -815,12 +815,28 @@ class AssignmentFlag(LabelRangeFlag):
                 'reference)' % (self.dev.device,))
 
 
+def _class_weight_table(class_weight, classes, device):
+    """The ``class_weight`` argument of the weighted focal-loss entries as they read it: fp32 [C + 1], contiguous, on the
+    logits' device (one factor per label value; index C = the empty label).  Checked, never converted: a conversion here
+    would be a copy per step, and a table the caller overwrites in place must stay the one a captured step reads."""
+    if not torch.is_tensor(class_weight):
+        raise TypeError('class_weight must be a tensor')
+    if class_weight.dtype != torch.float32 or not class_weight.is_contiguous() or class_weight.device != device:
+        raise ValueError('class_weight must be a contiguous fp32 tensor on %s' % (device,))
+    if tuple(class_weight.shape) != (classes + 1,):
+        raise ValueError('class_weight must be [%d] (one factor per label in [0, %d]), got %s'
+                         % (classes + 1, classes, tuple(class_weight.shape)))
+    return class_weight.detach()
+
+
 class SigmoidFocalLossSumFunction(Function):
     """sum over all elements of mmdet's sigmoid focal loss (ver_focal_loss_forward / _backward):
-    logits fp32|bf16 [N, C] with C % 8 == 0, target int64 [N] in [0, C]; returns an fp32 scalar."""
+    logits fp32|bf16 [N, C] with C % 8 == 0, target int64 [N] in [0, C]; returns an fp32 scalar.
+    ``class_weight`` (fp32 [C + 1] or None): row n is multiplied by class_weight[target[n]] (the ``_cw`` entries); no
+    gradient flows to it."""
 
     @staticmethod
-    def forward(ctx, logits, target, gamma, alpha):
+    def forward(ctx, logits, target, gamma, alpha, class_weight=None):
         logits = _gpu(logits, 'logits')
         if logits.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError('logits must be fp32 or bf16')
@@ -834,28 +850,39 @@ class SigmoidFocalLossSumFunction(Function):
         partial = torch.zeros(blocks, dtype=torch.float32, device=logits.device)
         flag = LabelRangeFlag.of(logits.device)
         flag.poll()                                          # a bad label of an EARLIER call is reported here
-        _launch('ver_focal_loss_forward', lambda: lib().ver_focal_loss_forward(
-            _p(logits), _p(target), _p(partial), n, c, gamma, alpha, dt, _p(flag.dev), _stream()))
+        if class_weight is None:
+            _launch('ver_focal_loss_forward', lambda: lib().ver_focal_loss_forward(
+                _p(logits), _p(target), _p(partial), n, c, gamma, alpha, dt, _p(flag.dev), _stream()))
+            ctx.save_for_backward(logits, target)
+        else:
+            table = _class_weight_table(class_weight, c, logits.device)
+            _launch('ver_focal_loss_forward_cw', lambda: lib().ver_focal_loss_forward_cw(
+                _p(logits), _p(target), _p(table), _p(partial), n, c, gamma, alpha, dt, _p(flag.dev), _stream()))
+            ctx.save_for_backward(logits, target, table)
         flag.mirror(c)
-        ctx.save_for_backward(logits, target)
         ctx.cfg = (gamma, alpha, dt)
         return partial.sum()
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        logits, target = ctx.saved_tensors
+        logits, target = ctx.saved_tensors[:2]
         gamma, alpha, dt = ctx.cfg
         n, c = logits.shape
         scale = _gpu(grad_out, 'grad_out').float().reshape(1).contiguous()
         grad = torch.empty_like(logits)
-        _launch('ver_focal_loss_backward', lambda: lib().ver_focal_loss_backward(
-            _p(logits), _p(target), _p(scale), _p(grad), n, c, gamma, alpha, dt, _stream()))
-        return grad, None, None, None
+        if len(ctx.saved_tensors) == 2:
+            _launch('ver_focal_loss_backward', lambda: lib().ver_focal_loss_backward(
+                _p(logits), _p(target), _p(scale), _p(grad), n, c, gamma, alpha, dt, _stream()))
+        else:
+            table = ctx.saved_tensors[2]
+            _launch('ver_focal_loss_backward_cw', lambda: lib().ver_focal_loss_backward_cw(
+                _p(logits), _p(target), _p(table), _p(scale), _p(grad), n, c, gamma, alpha, dt, _stream()))
+        return grad, None, None, None, None
 
 
-def sigmoid_focal_loss_sum(logits, target, gamma=2.0, alpha=0.25):
-    return SigmoidFocalLossSumFunction.apply(logits, target, float(gamma), float(alpha))
+def sigmoid_focal_loss_sum(logits, target, gamma=2.0, alpha=0.25, class_weight=None):
+    return SigmoidFocalLossSumFunction.apply(logits, target, float(gamma), float(alpha), class_weight)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1029,7 +1056,7 @@ class OccMLPFocalLossFunction(Function):
     ``grad_scale``.  No backward pass of the focal loss over the [N, 16] tensor, no scaled copy of it."""
 
     @staticmethod
-    def forward(ctx, x, g1, be1, w2, b2, g2, be2, w3, b3, target, eps, gamma, alpha, centered):
+    def forward(ctx, x, g1, be1, w2, b2, g2, be2, w3, b3, target, eps, gamma, alpha, centered, class_weight=None):
         x = _gpu(x, 'x').contiguous()
         _, vec, logits, rstd = _occ_mlp_forward_packed(x, None, None, g1, be1, w2, b2, g2, be2, w3, b3, eps, centered,
                                                        save_rstd=True)
@@ -1045,9 +1072,15 @@ class OccMLPFocalLossFunction(Function):
         partial = torch.zeros(blocks, dtype=torch.float32, device=x.device)
         flag = LabelRangeFlag.of(x.device)
         flag.poll()
-        entry = lib().ver_focal_loss_forward_grad_u8 if as_bytes else lib().ver_focal_loss_forward_grad
-        _launch('ver_focal_loss_forward_grad', lambda: entry(
-            _p(l2), _p(target), _p(partial), _p(l2), n, 16, gamma, alpha, 1, _p(flag.dev), _stream()))                      # (in place: the logits buffer now holds d loss / d logits)
+        if class_weight is None:
+            entry = lib().ver_focal_loss_forward_grad_u8 if as_bytes else lib().ver_focal_loss_forward_grad
+            _launch('ver_focal_loss_forward_grad', lambda: entry(
+                _p(l2), _p(target), _p(partial), _p(l2), n, 16, gamma, alpha, 1, _p(flag.dev), _stream()))                  # (in place: the logits buffer now holds d loss / d logits)
+        else:                                                 # ... times the row's class weight: the MLP backward is the same
+            table = _class_weight_table(class_weight, 16, x.device)
+            entry = lib().ver_focal_loss_forward_grad_u8_cw if as_bytes else lib().ver_focal_loss_forward_grad_cw
+            _launch('ver_focal_loss_forward_grad_cw', lambda: entry(
+                _p(l2), _p(target), _p(table), _p(partial), _p(l2), n, 16, gamma, alpha, 1, _p(flag.dev), _stream()))
         flag.mirror(16)
         ctx.save_for_backward(x, vec, w2.detach(), w3.detach(), l2, *((rstd,) if ctx.has_rstd else ()))
         ctx.eps, ctx.centered = eps, bool(centered)
@@ -1060,11 +1093,13 @@ class OccMLPFocalLossFunction(Function):
         rstd = ctx.saved_tensors[5] if ctx.has_rstd else None
         gscale = _gpu(grad_out, 'grad_out').float().reshape(1).contiguous()
         gx, vecs, dw2, dw3, db3 = _occ_mlp_backward_fused(x.view(-1, 128), gl, w2, w3, vec, rstd, ctx.eps, ctx.centered, gscale)
-        return (gx.view(x.shape), vecs[0], vecs[1], dw2, vecs[5], vecs[3], vecs[4], dw3, db3, None, None, None, None, None)
+        return (gx.view(x.shape), vecs[0], vecs[1], dw2, vecs[5], vecs[3], vecs[4], dw3, db3, None, None, None, None, None, None)
 
 
-def occ_mlp_focal_loss_sum(x, g1, be1, w2, b2, g2, be2, w3, b3, target, eps=1e-5, gamma=2.0, alpha=0.25, centered=False):
-    return OccMLPFocalLossFunction.apply(x, g1, be1, w2, b2, g2, be2, w3, b3, target, eps, float(gamma), float(alpha), centered)
+def occ_mlp_focal_loss_sum(x, g1, be1, w2, b2, g2, be2, w3, b3, target, eps=1e-5, gamma=2.0, alpha=0.25, centered=False,
+                           class_weight=None):
+    return OccMLPFocalLossFunction.apply(x, g1, be1, w2, b2, g2, be2, w3, b3, target, eps, float(gamma), float(alpha), centered,
+                                         class_weight)
 
 
 def occ_mlp(x, w1, b1, g1, be1, w2, b2, g2, be2, w3, b3, eps=1e-5, centered=False):
