@@ -43,6 +43,9 @@ extern "C" {
 #define VER_F32  0
 #define VER_BF16 1
 
+#define VER_I32  0            /* index dtypes (ver_occ_targets) */
+#define VER_I64  1
+
 int         ver_abi_version(void);
 const char* ver_last_error(void);
 
@@ -477,6 +480,17 @@ int ver_occ_mlp_backward_fused(const void* x, const void* grad_logits, const flo
 int ver_occ_mlp_backward_fused_stats(const void* x, const void* grad_logits, const float* W2, const float* W3,
                                      const float* vectors, const float* rstd, void* grad_x, float* param_grads, long N,
                                      int width, int classes, float eps, const float* grad_scale, int flags, void* stream);
+/*   the same with REPRODUCIBLE parameter gradients (additive to ABI 31): the two entries above add every workgroup's share of
+ *   param_grads with float atomics, so their last bits follow the arrival order and differ from run to run.  Here workgroup w
+ *   adds into its own zeroed slab, slabs f32 [workgroups][6*width + classes*width + classes + width*width] (scratch, at least
+ *   ver_occ_mlp_backward_fused_slab_bytes(N) bytes, 4-byte aligned), and one more launch sums the slabs in a fixed order into
+ *   param_grads: the same inputs give the same bits.  grad_x is the same kernel's and was reproducible already.  Two more
+ *   launches (zeroing the slabs, the sum: 19.7 MB each way at 256 workgroups) on a kernel of milliseconds. */
+long ver_occ_mlp_backward_fused_slab_bytes(long N);
+int ver_occ_mlp_backward_fused_slabs(const void* x, const void* grad_logits, const float* W2, const float* W3,
+                                     const float* vectors, const float* rstd, void* grad_x, float* param_grads, float* slabs,
+                                     long slab_bytes, long N, int width, int classes, float eps, const float* grad_scale,
+                                     int flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Occupancy post-processing: VoxelFormerOccupancyHead.get_occupancy_prediction, focal-loss branch
@@ -797,6 +811,48 @@ int ver_det_set_loss_backward(const void* cls, int cls_dtype, const float* box, 
 int ver_det_decode(const void* cls, int cls_dtype, const float* box, int box_ld, float* out_boxes, float* out_scores,
                    int32_t* out_labels, uint8_t* out_valid, int32_t* out_query, const float* center_range,
                    float score_threshold, int flags, int B, int Q, int C, int K, int codes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Occupancy targets on the device (additive to ABI 31; csrc/ver_targets.hip): the dataset's sparse occupancy annotation of a
+ * whole batch -> one byte label per voxel and the number of occupied voxels, in place of the reference's per-sample
+ * `gt_occupancy = full(voxel_num, classes); gt_occupancy[idx] = cls` on an int64 volume (head:1322-1326, :1404-1408) and of
+ * the label volume of MP3DDataset.evaluate_occ_iou (mp3docc_dataset.py:500-514).
+ *   pairs           i32 | i64 [n_total][2] (flat voxel index, class) of all samples, one after the other (pair_dtype =
+ *                   VER_I32 | VER_I64; aligned to one pair); may be NULL when n_total == 0
+ *   offsets         i32 device [bs + 1]: sample b owns pairs [offsets[b], offsets[b+1]); clamped into [0, n_total];
+ *                   an empty sample is legal
+ *   invalid         i32 | i64 [n_invalid] flat voxel indices (invalid_dtype), invalid_offsets i32 device [bs + 1]; both may
+ *                   be NULL when n_invalid == 0: the evaluation form
+ *   row_table       i32 [voxel_num / zdim][3] = (group offset, group n_rows, index within the group) of every lattice
+ *                   position q, or NULL.  The label of sample b, voxel v = z * rows + q (rows = voxel_num / zdim; the
+ *                   reference's (Z, X, Y) order) is byte (bs * off[q] + b * n[q] + loc[q]) * zdim + z -- the group-major row
+ *                   order the occupancy GEMMs leave their rows in (dense_heads/occ_proj_lattice.py) -- and byte
+ *                   b * voxel_num + v with a NULL table.  The table does not depend on bs.  A table entry that points
+ *                   outside the buffer writes nothing and counts in bad[0].
+ *   labels          u8 [bs * voxel_num], 4-byte aligned and ALLOCATED ROUNDED UP to a multiple of 4 bytes; written in full,
+ *                   whatever it held (the padding bytes too)
+ *   count           i32 [bs + 1], written: occupied voxels of every sample, then their total
+ *   bad             i32 [2], written (see below)
+ * SEMANTICS.  Every voxel starts as `classes` (empty).  A pair (v, c) with 0 <= v < voxel_num and 0 <= c < classes sets voxel
+ * v of its sample to c; c == classes names the empty label and writes nothing; any other pair is skipped and counted in bad[0]
+ * (the reference raises there).  With distinct voxel indices per sample the result is the reference's, byte for byte.
+ * OUR DEFINITION where the reference's is undefined (a voxel listed several times: on a GPU its index_put_ leaves the winner
+ * open, on the CPU the last pair stays): the LARGEST class stays, whatever the order of the pairs.  bad[1] = the number of
+ * pairs (c < classes) whose voxel ends up with another class than theirs -- the listings that lost; 0 exactly when no voxel
+ * is listed with two different classes, and independent of the order of the pairs.  Repeats of one class count nothing.
+ * count[b] counts the voxels of sample b that left the empty state, each once: (labels < classes).sum() per sample before
+ * the invalid pass, exact under repeats.
+ * Invalid voxels are set to 255 after all pairs, in a later kernel of the same call, and override any pair; out-of-range
+ * entries count in bad[0].  count stays the pairs' count (the evaluation never reads it).
+ * Per-byte read-modify-write = a 32-bit compare-and-swap on the aligned word holding the byte (relaxed, agent scope).  Four
+ * launches at most (fill, pairs, verify, invalid), the fill being a kernel: no memset node, no allocation, no host read --
+ * the call can be captured.  Supported: bs * voxel_num < 2^31, classes < 255, voxel_num % zdim == 0, bs < 65 536
+ * (VER_EUNSUPPORTED beyond); bs == 0 returns 0 and launches nothing.
+ */
+int ver_occ_targets(const void* pairs, int pair_dtype, const int32_t* offsets, long n_total, const void* invalid,
+                    int invalid_dtype, const int32_t* invalid_offsets, long n_invalid, const int32_t* row_table,
+                    uint8_t* labels, int32_t* count, int32_t* bad, long voxel_num, int zdim, int classes, int bs,
+                    void* stream);
 
 #ifdef __cplusplus
 }

@@ -1140,7 +1140,7 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
                                                         const float* __restrict__ vec, __bf16* __restrict__ dx,
                                                         float* __restrict__ pgrad, long N, float eps,
                                                         const float* __restrict__ grad_scale,
-                                                        const float* __restrict__ rstd) {
+                                                        const float* __restrict__ rstd, long pgrad_stride) {
     constexpr int OT = 2, RT = 4, KS = 2;
     const float gscale = grad_scale ? grad_scale[0] : 1.0f;        // scalar factor of d(logits) (device-side, may be null)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1700,7 +1700,10 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
         }
     }
     WS_SPAN(1);
-    // ---- parameter gradients: one atomic per element and workgroup
+    // ---- parameter gradients: one atomic per element and workgroup.  pgrad_stride != 0 (ver_occ_mlp_backward_fused_slabs):
+    // into this workgroup's own zeroed slab, where the add is the only one its element gets -- k_pgrad_reduce then sums the
+    // slabs in a fixed order and the result does not depend on which workgroup arrives first
+    pgrad += (long)blockIdx.x * pgrad_stride;
 #pragma unroll
     for (int ot = 0; ot < OT; ++ot) {
 #pragma unroll
@@ -1726,40 +1729,94 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
     }
 }
 
+constexpr int kPgradFloats = 6 * kW + kC * kW + kC + kW * kW;
+constexpr long kWsMaxGrid = 256;                          // one workgroup per CU (LDS bound), persistent
+
+// out[e] = slab[0][e] + slab[1][e] + ... in that order (ver_occ_mlp_backward_fused_slabs): eight loads in flight, one chain of adds
+__global__ __launch_bounds__(256) void k_pgrad_reduce(const float* __restrict__ slabs, int nslabs, float* __restrict__ out) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= kPgradFloats) return;
+    float s = 0.0f;
+    int b = 0;
+    for (; b + 8 <= nslabs; b += 8) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = slabs[(long)(b + j) * kPgradFloats + e];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += v[j];
+    }
+    for (; b < nslabs; ++b) s += slabs[(long)b * kPgradFloats + e];
+    out[e] = s;
+}
+
+static long ws_grid(long N) {
+    const long nb = (N + kWsRows - 1) / kWsRows;
+    return nb < kWsMaxGrid ? nb : kWsMaxGrid;
+}
+
+static int occ_mlp_backward_fused(const char* who, const void* x, const void* grad_logits, const float* W2, const float* W3,
+                                  const float* vectors, const float* rstd, void* grad_x, float* param_grads, float* slabs,
+                                  long slab_bytes, long N, int width, int classes, float eps, const float* grad_scale, int flags,
+                                  void* stream) {
+    VER_REQUIRE(N >= 0, VER_EINVAL, "%s: negative row count", who);
+    VER_REQUIRE((flags & ~VER_OCC_MLP_CENTERED) == 0, VER_EINVAL, "%s: unknown flags 0x%x", who, flags);
+    VER_REQUIRE(width == kW && classes == kC, VER_EUNSUPPORTED, "%s: built for width %d / %d classes (got %d / %d)", who, kW, kC,
+                width, classes);
+    VER_REQUIRE(W2 && W3 && vectors && param_grads, VER_EINVAL, "%s: null pointer argument", who);
+    hipStream_t st = (hipStream_t)stream;
+    const long gridw = ws_grid(N);
+    const size_t need = (size_t)gridw * kPgradFloats * sizeof(float);
+    if (slabs || slab_bytes) {
+        VER_REQUIRE(slab_bytes >= 0 && (size_t)slab_bytes >= need && (slabs || need == 0) && ((uintptr_t)slabs & 3) == 0, VER_EINVAL,
+                    "%s: %ld bytes of slabs at %p, %zu needed (ver_occ_mlp_backward_fused_slab_bytes)", who, slab_bytes,
+                    (void*)slabs, need);
+    }
+    const bool slabbed = slabs && N > 0;
+    if (int zrc = slabbed ? ver_zero_async(slabs, need, st) : ver_zero_async(param_grads, kPgradFloats * sizeof(float), st)) return zrc;
+    if (N == 0) return VER_OK;
+    VER_REQUIRE(x && grad_logits && grad_x, VER_EINVAL, "%s: null pointer argument", who);
+    VER_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)grad_x & 15) == 0 && ((uintptr_t)grad_logits & 15) == 0 &&
+                    ((uintptr_t)W2 & 15) == 0,
+                VER_EINVAL, "%s: buffers must be 16-byte aligned", who);
+    // (the saved statistics replace the recomputation only on centred rows; otherwise they are ignored)
+    const bool use_rstd = rstd && (flags & VER_OCC_MLP_CENTERED);
+    auto kern = (flags & VER_OCC_MLP_CENTERED) ? (use_rstd ? k_occ_mlp_bwd_ws<true, true> : k_occ_mlp_bwd_ws<true, false>)
+                                               : k_occ_mlp_bwd_ws<false, false>;
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWsLds);
+    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "%s: LDS attribute: %s", who, hipGetErrorString(e));
+    hipLaunchKernelGGL(kern, dim3((unsigned)gridw), dim3(512), kWsLds, st, (const __bf16*)x, (const __bf16*)grad_logits, W2,
+                       W3, vectors, (__bf16*)grad_x, slabbed ? slabs : param_grads, N, eps, grad_scale,
+                       use_rstd ? rstd : nullptr, slabbed ? (long)kPgradFloats : 0L);
+    int rc = ver_check_launch(who);
+    if (rc || !slabbed) return rc;
+    hipLaunchKernelGGL(k_pgrad_reduce, dim3((kPgradFloats + 255) / 256), dim3(256), 0, st, slabs, (int)gridw, param_grads);
+    return ver_check_launch(who);
+}
+
 extern "C" int ver_occ_mlp_backward_fused(const void* x, const void* grad_logits, const float* W2, const float* W3,
                                           const float* vectors, void* grad_x, float* param_grads, long N, int width,
                                           int classes, float eps, const float* grad_scale, int flags, void* stream) {
-    return ver_occ_mlp_backward_fused_stats(x, grad_logits, W2, W3, vectors, nullptr, grad_x, param_grads, N, width, classes,
-                                            eps, grad_scale, flags, stream);
+    return occ_mlp_backward_fused("ver_occ_mlp_backward_fused", x, grad_logits, W2, W3, vectors, nullptr, grad_x, param_grads,
+                                  nullptr, 0, N, width, classes, eps, grad_scale, flags, stream);
 }
 
 extern "C" int ver_occ_mlp_backward_fused_stats(const void* x, const void* grad_logits, const float* W2, const float* W3,
                                                 const float* vectors, const float* rstd, void* grad_x, float* param_grads,
                                                 long N, int width, int classes, float eps, const float* grad_scale, int flags,
                                                 void* stream) {
-    VER_REQUIRE(N >= 0, VER_EINVAL, "ver_occ_mlp_backward_fused: negative row count");
-    VER_REQUIRE((flags & ~VER_OCC_MLP_CENTERED) == 0, VER_EINVAL, "ver_occ_mlp_backward_fused: unknown flags 0x%x", flags);
-    VER_REQUIRE(width == kW && classes == kC, VER_EUNSUPPORTED,
-                "ver_occ_mlp_backward_fused: built for width %d / %d classes (got %d / %d)", kW, kC, width, classes);
-    VER_REQUIRE(W2 && W3 && vectors && param_grads, VER_EINVAL, "ver_occ_mlp_backward_fused: null pointer argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (int zrc = ver_zero_async(param_grads, (6 * kW + kC * kW + kC + kW * kW) * sizeof(float), st)) return zrc;   // (kernel: ver_zero_async)
-    hipError_t e = hipSuccess;
-    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_occ_mlp_backward_fused: memset: %s", hipGetErrorString(e));
-    if (N == 0) return VER_OK;
-    VER_REQUIRE(x && grad_logits && grad_x, VER_EINVAL, "ver_occ_mlp_backward_fused: null pointer argument");
-    VER_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)grad_x & 15) == 0 && ((uintptr_t)grad_logits & 15) == 0 &&
-                    ((uintptr_t)W2 & 15) == 0,
-                VER_EINVAL, "ver_occ_mlp_backward_fused: buffers must be 16-byte aligned");
-    // (the saved statistics replace the recomputation only on centred rows; otherwise they are ignored)
-    const bool use_rstd = rstd && (flags & VER_OCC_MLP_CENTERED);
-    auto kern = (flags & VER_OCC_MLP_CENTERED) ? (use_rstd ? k_occ_mlp_bwd_ws<true, true> : k_occ_mlp_bwd_ws<true, false>)
-                                               : k_occ_mlp_bwd_ws<false, false>;
-    e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWsLds);
-    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_occ_mlp_backward_fused: LDS attribute: %s", hipGetErrorString(e));
-    const long nb = (N + kWsRows - 1) / kWsRows;
-    const long gridw = nb < 256 ? nb : 256;               // one workgroup per CU (LDS bound), persistent
-    hipLaunchKernelGGL(kern, dim3((unsigned)gridw), dim3(512), kWsLds, st, (const __bf16*)x, (const __bf16*)grad_logits, W2,
-                       W3, vectors, (__bf16*)grad_x, param_grads, N, eps, grad_scale, use_rstd ? rstd : nullptr);
-    return ver_check_launch("ver_occ_mlp_backward_fused");
+    return occ_mlp_backward_fused("ver_occ_mlp_backward_fused", x, grad_logits, W2, W3, vectors, rstd, grad_x, param_grads, nullptr,
+                                  0, N, width, classes, eps, grad_scale, flags, stream);
+}
+
+extern "C" long ver_occ_mlp_backward_fused_slab_bytes(long N) {
+    return N <= 0 ? 0 : ws_grid(N) * kPgradFloats * (long)sizeof(float);
+}
+
+extern "C" int ver_occ_mlp_backward_fused_slabs(const void* x, const void* grad_logits, const float* W2, const float* W3,
+                                                const float* vectors, const float* rstd, void* grad_x, float* param_grads,
+                                                float* slabs, long slab_bytes, long N, int width, int classes, float eps,
+                                                const float* grad_scale, int flags, void* stream) {
+    VER_REQUIRE(slabs || N <= 0, VER_EINVAL, "ver_occ_mlp_backward_fused_slabs: null slabs");
+    return occ_mlp_backward_fused("ver_occ_mlp_backward_fused_slabs", x, grad_logits, W2, W3, vectors, rstd, grad_x, param_grads,
+                                  slabs, slab_bytes, N, width, classes, eps, grad_scale, flags, stream);
 }

@@ -211,6 +211,32 @@ def _row_index(plan, bs, device):
     return plan._row_index[bs]
 
 
+def lattice_plan(C, Z, Hl, Wl, device):
+    """The plan of an even lattice [C, Z, Hl, Wl] (dense volume [C, Z, 2 Hl, 2 Wl]) on ``device``, or None: the one
+    ``get_plan`` call of ``occ_proj_from_lattice``, which whoever orders targets for its rows (the head's
+    ``occupancy_targets_device``) makes through here as well."""
+    return get_plan(C, Z, 2 * Hl, 2 * Wl, torch.device(device))
+
+
+def row_table(plan, device=None):
+    """int32 [rows, 3] = (group offset, group n_rows, index within the group) of every position q: with them the buffer row
+    of (sample b, position q) in a ``bs``-sample batch is ``bs * offset + b * n_rows + index`` -- ``_row_index(plan, bs)[0]``
+    for every bs from one table (``ver_occ_targets`` reads it).  Built once per plan; ``device=None``: numpy, on the host."""
+    if '_row_table' not in plan.__dict__:
+        table = np.empty((plan.rows, 3), dtype=np.int32)
+        for g in plan.groups:
+            table[g.members, 0], table[g.members, 1] = g.offset, g.n_rows
+            table[g.members, 2] = np.arange(g.n_rows)
+        plan._row_table = (table, {})
+    table, on = plan._row_table
+    if device is None:
+        return table
+    key = str(torch.device(device))
+    if key not in on:
+        on[key] = torch.from_numpy(table).to(device)
+    return on[key]
+
+
 def _token_matrix(plan, like):
     """[Z*C, groups*Z] 0/1 (counts): column (g, k) marks the non-data columns of token k in group g (``ncols_by_token``);
     built once per plan and dtype."""
@@ -399,7 +425,7 @@ def occ_proj_from_lattice(e, up_bias, weight, bias):
         Hl, Wl = 2 * hh, 2 * wh
     else:
         bs, Z, Hl, Wl, C = e.shape
-    plan = get_plan(C, Z, 2 * Hl, 2 * Wl, e.device)
+    plan = lattice_plan(C, Z, Hl, Wl, e.device)
     if plan is None:
         return None
     return _OccProjLattice.apply(e, up_bias, weight, bias, plan), plan

@@ -29,7 +29,7 @@ from . import coders, losses  # noqa: F401  (registers NMSFreeCoder / FocalLoss 
 from .assigner import SamplingResult, build_assigner
 from .coders import normalize_bbox
 from ..ddp import reduce_mean
-from .occ_proj_lattice import occ_proj_from_lattice, rows_to_voxels, voxels_to_rows
+from .occ_proj_lattice import lattice_plan, occ_proj_from_lattice, row_table, rows_to_voxels, voxels_to_rows
 from .row_linear import row_linear
 from .upsample import full_volume, is_reference_geometry, upsample_lattice
 
@@ -47,6 +47,47 @@ def _mean_over_ranks(value, like):
 # Ground truth of a batch in static shapes (``VoxelFormerOccupancyHead.pad_gts``), all on the device: boxes [bs, cap, 9]
 # (gravity centre, dims, yaw, zero velocity; rows >= counts[b] are padding), labels int64 [bs, cap], counts int32 [bs].
 PaddedGts = collections.namedtuple('PaddedGts', 'boxes labels counts')
+
+
+class OccupancyTargets:
+    """Occupancy targets of a batch in static shapes, as ``VoxelFormerOccupancyHead.occupancy_targets_device`` builds them
+    from the sparse annotation in one launch sequence (``hipops.occ_targets``); accepted wherever the dense ``[bs,
+    voxel_num]`` tensor is.  ``labels`` uint8 [bs * voxel_num]: ``classes`` = empty, 255 = not evaluated; ``order`` says where
+    a voxel's byte sits: ``'voxels'`` = the reference's (Z, X, Y) order per sample, ``'rows'`` = the group-major row order
+    of the occupancy GEMMs of ``plan`` (the bytes the loss kernels read next to the logit rows, as they are).  ``count``
+    int32 [bs + 1]: occupied voxels per sample and their total (``count[-1]`` is the losses' ``avg_factor``); ``bad`` int32
+    [2]: rejected pairs, and listings of a voxel that lost to a larger class."""
+
+    def __init__(self, labels, count, bad, order, bs, plan=None, zdim=1):
+        if order not in ('rows', 'voxels') or (order == 'rows' and plan is None):
+            raise ValueError("OccupancyTargets: order is 'voxels', or 'rows' with the plan the rows belong to")
+        self.labels, self.count, self.bad, self.order, self.bs, self.plan, self.zdim = labels, count, bad, order, bs, plan, zdim
+
+    def check(self):
+        """Read ``bad`` on the host (a device -> host synchronisation) and raise ``ValueError`` when a counter is set."""
+        rejected, lost = (int(v) for v in self.bad.tolist())
+        if rejected or lost:
+            what = []
+            if rejected:
+                what.append('bad[0] = %d: pairs or invalid voxels with an index or a class out of range were skipped '
+                            '(the reference raises on them)' % rejected)
+            if lost:
+                what.append('bad[1] = %d: listings of a voxel that lost to a larger class of the same voxel' % lost)
+            raise ValueError('occupancy annotation: ' + '; '.join(what))
+        return self
+
+    def ordered(self, order, plan=None):
+        """``labels`` (uint8 [bs * voxel_num]) in ``order``: as they are when that is their order, else permuted once with
+        the plan's row maps -- the only place where targets of this kind change their order."""
+        if order == self.order and (order == 'voxels' or plan is self.plan):
+            return self.labels
+        z = self.zdim
+        voxels = self.labels
+        if self.order == 'rows':
+            voxels = rows_to_voxels(self.labels.view(-1, z), self.plan, self.bs).permute(0, 2, 1).reshape(-1)
+        if order == 'voxels':
+            return voxels
+        return voxels_to_rows(voxels.view(self.bs, z, plan.rows).permute(0, 2, 1), plan, self.bs).reshape(-1)
 
 
 def _to_device_async(t, dev):
@@ -302,6 +343,21 @@ class VoxelFormerOccupancyHead(BaseModule):
             voxel_embed = lowp
         return voxel_embed.contiguous()
 
+    def _lattice_geometry(self):
+        """The head's geometry takes the lattice path: three reference-geometry ConvTranspose3d layers to 8x the query grid."""
+        convs = list(self.up_sample) if self.refine_occ else []
+        return (self.refine_occ and self.bev_z != self.occ_zdim and len(convs) == 3
+                and all(is_reference_geometry(m) for m in convs)
+                and 8 * self.bev_h == self.occ_xdim and 8 * self.bev_w == self.occ_ydim)
+
+    def occupancy_row_plan(self, device):
+        """The plan whose row order ``occupancy_from_volume(..., rows_only=True)`` leaves its logits in on ``device``, or None
+        where the head takes the dense path: the lattice after the three upsampling layers is [C, bev_z, 4 bev_h, 4 bev_w],
+        and ``lattice_plan`` is the call ``occ_proj_from_lattice`` makes for it."""
+        if not self._lattice_geometry():
+            return None
+        return lattice_plan(self.embed_dims, self.bev_z, 4 * self.bev_h, 4 * self.bev_w, device)
+
     def _occ_rows_from_lattice(self, voxel_embed):
         """The lattice path of ``occupancy_from_volume`` up to the rows ``occ_branches`` reads: voxel_embed as
         ``_volume_input`` returns it -> ``(rows [bs*X*Y, Z*occ_dims] in group-major GEMM order, plan, fold)``, or None
@@ -313,8 +369,7 @@ class VoxelFormerOccupancyHead(BaseModule):
         c = self.embed_dims
         x = voxel_embed.view(bs, c, self.bev_z, self.bev_h, self.bev_w)          # raw view :558
         convs = list(self.up_sample)
-        if (self.bev_z != self.occ_zdim and len(convs) == 3 and all(is_reference_geometry(m) for m in convs)
-                and 8 * self.bev_h == self.occ_xdim and 8 * self.bev_w == self.occ_ydim):
+        if self._lattice_geometry():
             # lattice path: neither the dense volume nor its 3/4 constant columns are formed
             e, b_up = upsample_lattice(x, [m.weight for m in convs], [m.bias for m in convs])
             # ``occ_proj`` (:571) is followed by ``occ_branches[0]`` = Linear(128, 128) on every 128-slice of
@@ -417,6 +472,15 @@ class VoxelFormerOccupancyHead(BaseModule):
         from ..hipops import occ_mlp_focal_loss_sum
         _, n1, _, l2, n2, _, l3 = list(self.occ_branches)
         lo = self.loss_occupancy
+        if isinstance(gt_occupancy, OccupancyTargets):
+            # byte labels already in the rows' order and the occupied count: nothing to clamp, narrow, permute or reduce
+            gt, avg = gt_occupancy.ordered('rows', plan), gt_occupancy.count[-1] * 1.0
+            with torch.autocast('cuda', enabled=False):
+                w2c, b2c = self._centered(l2.weight.float(), l2.bias.float())
+                s = occ_mlp_focal_loss_sum(x.to(torch.bfloat16), n1.weight, n1.bias, w2c, b2c, n2.weight, n2.bias,
+                                           l3.weight, l3.bias, gt, n1.eps, lo.gamma, lo.alpha, centered=True,
+                                           class_weight=class_weight)
+            return torch.nan_to_num(lo.loss_weight * (s / avg))
         lo.check_label_range(gt_occupancy, self.occupancy_classes)      # (the same first-call host check as FocalLoss.forward)
         # the labels are permuted into the GEMMs' row order and counted as BYTES (17 classes): int64 labels made the
         # permutation and the count three passes over 0.77 GB each at 192 viewpoints (1.4 ms; now 0.3 with the narrowing copy).
@@ -645,6 +709,8 @@ class VoxelFormerOccupancyHead(BaseModule):
         normalised by the number of occupied voxels, NaN-guarded.  ``class_weights`` (``class_weight_table``): every row
         times the factor of its label, as ``loss_only_occupancy`` does with ``occ_weights`` (head:1417-1425); the
         normaliser stays the unweighted count."""
+        if isinstance(gt_occupancy, OccupancyTargets):
+            return self._occupancy_loss_of_targets(occupancy_preds, gt_occupancy, class_weights)
         if isinstance(occupancy_preds, tuple):                         # (logits in GEMM row order, plan, bs)
             occupancy_preds, plan, bs = occupancy_preds               # [bs*X*Y, Z, classes], group-major rows
             gt = gt_occupancy.reshape(bs, self.occ_zdim, plan.rows).permute(0, 2, 1)   # (Z, X, Y) order -> [bs, X*Y, Z]
@@ -655,6 +721,25 @@ class VoxelFormerOccupancyHead(BaseModule):
         gt = gt_occupancy.reshape(-1)
         avg = (gt < self.occupancy_classes).sum() * 1.0
         table = self.class_weight_table(class_weights, preds.device)
+        if table is None:
+            return torch.nan_to_num(self.loss_occupancy(preds, gt, avg_factor=avg))
+        return torch.nan_to_num(self.loss_occupancy(preds, gt, avg_factor=avg, class_weight=table))
+
+    def _occupancy_loss_of_targets(self, occupancy_preds, targets, class_weights=None):
+        """``occupancy_loss`` against an ``OccupancyTargets``: its labels in the order of the logits (the row order for the
+        row-order tuple) and ``count[-1]`` as the normaliser -- no compare, no reduction over the labels.  The registered
+        loss takes int64 targets (``ver_focal_loss_forward``, ``F.one_hot``): the bytes are widened here."""
+        if isinstance(occupancy_preds, tuple):                         # (logits in GEMM row order, plan, bs)
+            occupancy_preds, plan, _ = occupancy_preds
+            gt = targets.ordered('rows', plan)
+        else:
+            gt = targets.ordered('voxels')
+        preds = occupancy_preds.reshape(-1, self.occupancy_classes)
+        if not (preds.is_cuda and preds.dtype == torch.bfloat16):     # the fused loss reads bf16 as is
+            preds = preds.float()
+        avg = targets.count[-1].to(preds.device) * 1.0
+        table = self.class_weight_table(class_weights, preds.device)
+        gt = gt.to(preds.device).long()
         if table is None:
             return torch.nan_to_num(self.loss_occupancy(preds, gt, avg_factor=avg))
         return torch.nan_to_num(self.loss_occupancy(preds, gt, avg_factor=avg, class_weight=table))
@@ -786,6 +871,43 @@ class VoxelFormerOccupancyHead(BaseModule):
                 gt[b, pairs[:, 0]] = pairs[:, 1]
         return gt
 
+    def occupancy_targets_device(self, occ_gts, invalid=None, rows=None, device=None):
+        """``occupancy_targets`` (and, with ``invalid``, ``occupancy_eval_labels``) without the dense int64 volume and the
+        per-sample copies: ``occ_gts`` / ``invalid`` as those two take them -- or a ``hipops.PackedOccGts`` a loader packed
+        (and perhaps copied) ahead of time -- go to the device as ONE asynchronous copy and become an ``OccupancyTargets``
+        in one ``ver_occ_targets`` call.  ``rows``: None = the GEMMs' row order exactly when the head's geometry has a
+        lattice plan (``occupancy_row_plan``), the reference's voxel order otherwise; False = the voxel order; True = the
+        row order where there is a plan.  On a CPU ``device`` the same contract in numpy (``hipops.occ_targets_host``).
+        ``bad`` is read on the host on a module's first call only (VER_FOCAL_CHECK=2: every call, 0: never; never under
+        stream capture), as ``FocalLoss.check_label_range`` reads its labels; ``OccupancyTargets.check()`` reads it on demand."""
+        from .. import hipops
+        from .losses import _FOCAL_CHECK
+        device = torch.device(device if device is not None else self.code_weights.device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if isinstance(occ_gts, hipops.PackedOccGts) and invalid is not None:
+            raise ValueError('occupancy_targets_device: a PackedOccGts carries its invalid voxels (pack_occ_gts(occ_gts, invalid)); '
+                             'pass one or the other')
+        packed = occ_gts if isinstance(occ_gts, hipops.PackedOccGts) else hipops.pack_occ_gts(occ_gts, invalid, pinned=device.type == 'cuda')
+        plan = self.occupancy_row_plan(device) if rows is not False else None
+        z, classes = self.occ_zdim, self.occupancy_classes
+        if device.type == 'cuda':
+            p = packed if packed.buffer.is_cuda else packed.to(device)
+            labels, count, bad = hipops.occ_targets(p.pairs, p.offsets, self.voxel_num, z, classes,
+                                                    row_table(plan, device) if plan is not None else None,
+                                                    p.invalid, p.invalid_offsets)
+        else:
+            p = packed if not packed.buffer.is_cuda else packed.to('cpu')
+            labels, count, bad = (torch.from_numpy(a) for a in hipops.occ_targets_host(
+                p.pairs.numpy(), p.offsets.numpy(), self.voxel_num, z, classes, row_table(plan) if plan is not None else None,
+                None if p.invalid is None else p.invalid.numpy(), None if p.invalid is None else p.invalid_offsets.numpy()))
+        targets = OccupancyTargets(labels, count, bad, 'rows' if plan is not None else 'voxels', packed.bs, plan, z)
+        capturing = device.type == 'cuda' and torch.cuda.is_current_stream_capturing()
+        if not capturing and (_FOCAL_CHECK >= 2 or (_FOCAL_CHECK == 1 and not self.__dict__.get('_occ_targets_checked'))):
+            self.__dict__['_occ_targets_checked'] = True
+            targets.check()
+        return targets
+
     def occupancy_eval_labels(self, occ_gts, occ_invalid=None, device=None):
         """The evaluation labels of ``MP3DDataset.evaluate_occ_iou`` (mp3docc_dataset.py:500-514) as bytes: ``occ_gts`` as
         in ``occupancy_targets``; ``occ_invalid[b]`` (or None) the voxel indices of the ``occ_invalid_path`` file, whose
@@ -818,8 +940,11 @@ class VoxelFormerOccupancyHead(BaseModule):
         nc = self.occupancy_classes
         if isinstance(occupancy_preds, tuple):                         # (logits in GEMM row order, plan, bs)
             logits, plan, bs = occupancy_preds                         # [bs*X*Y, Z, classes], group-major rows
-            gt = labels.reshape(bs, self.occ_zdim, plan.rows).permute(0, 2, 1)      # (Z, X, Y) order -> [bs, X*Y, Z]
-            gt = voxels_to_rows(gt, plan, bs)
+            if isinstance(labels, OccupancyTargets):
+                gt = labels.ordered('rows', plan).view(-1, self.occ_zdim)
+            else:
+                gt = labels.reshape(bs, self.occ_zdim, plan.rows).permute(0, 2, 1)      # (Z, X, Y) order -> [bs, X*Y, Z]
+                gt = voxels_to_rows(gt, plan, bs)
             if hist is None:
                 hist = torch.zeros((bs, len(thresholds), nc + 1, nc + 1), dtype=torch.int64, device=logits.device)
             # the rows of sample b in group g are contiguous (row bs*offset_g + b*n_g + i): one call per group
@@ -828,6 +953,8 @@ class VoxelFormerOccupancyHead(BaseModule):
                 _confusion(logits[sl], gt[sl], bs, thresholds, hist)
             return hist
         bs = occupancy_preds.shape[0] if occupancy_preds.dim() == 3 else 1
+        if isinstance(labels, OccupancyTargets):
+            labels = labels.ordered('voxels').to(occupancy_preds.device)
         if hist is None:
             hist = torch.zeros((bs, len(thresholds), nc + 1, nc + 1), dtype=torch.int64, device=occupancy_preds.device)
         return _confusion(occupancy_preds, labels, bs, thresholds, hist)
@@ -873,8 +1000,11 @@ class VoxelFormerOccupancyHead(BaseModule):
         from ..hipops import occ_mlp_confusion
         x, plan, bs = fused
         image, vec, eps = self._fused_eval_params()
-        gt = labels.reshape(bs, self.occ_zdim, plan.rows).permute(0, 2, 1)          # (Z, X, Y) order -> [bs, X*Y, Z]
-        gt = voxels_to_rows(gt.to(torch.uint8), plan, bs)
+        if isinstance(labels, OccupancyTargets):
+            gt = labels.ordered('rows', plan).view(-1, self.occ_zdim)
+        else:
+            gt = labels.reshape(bs, self.occ_zdim, plan.rows).permute(0, 2, 1)          # (Z, X, Y) order -> [bs, X*Y, Z]
+            gt = voxels_to_rows(gt.to(torch.uint8), plan, bs)
         if hist is None:
             hist = torch.zeros((bs, len(thresholds), nc + 1, nc + 1), dtype=torch.int64, device=x.device)
         z = self.occ_zdim

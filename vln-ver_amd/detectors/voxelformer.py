@@ -13,7 +13,8 @@ the MI355X design needs it to:
   the path (the reference reads ``img_metas[0]`` only, ``samples_per_gpu=1``); B = 1 reproduces it;
 * tensors go to the module's device, not to ``.cuda()`` unconditionally (same thing on a GPU box); the features cross
   PCIe as one asynchronous copy out of a pinned staging buffer; ``autocast_dtype`` / ``occupancy_rows`` (extra
-  constructor kwargs, off by default) select the bf16 training form that ``bench.py`` times;
+  constructor kwargs, off by default) select the bf16 training form that ``bench.py`` times; ``device_occupancy_targets``
+  (the same) builds the occupancy targets on the device from one copy of the sparse annotation;
 * the image backbone / neck / point-cloud branches the config still lists are **not built**: ``forward_train`` and
   ``simple_test`` never call ``extract_feat`` in the reference either (features are precomputed, :285-289), and a DDP
   replica without the never-executed ResNet-50 + FPN needs no ``find_unused_parameters``.
@@ -42,7 +43,7 @@ class VoxelFormer(BaseModule):
                  pts_bbox_head=None, img_roi_head=None, img_rpn_head=None, train_cfg=None, test_cfg=None,
                  pretrained=None, video_test_mode=False, keep_bev_history=False, use_occ_gts=True, only_occ=False,
                  only_det=False, add_layout=False, dataset_type='MP3DDataset', can_bus_in_dataset=True,
-                 init_cfg=None, autocast_dtype=None, occupancy_rows=False):
+                 init_cfg=None, autocast_dtype=None, occupancy_rows=False, device_occupancy_targets=False):
         super().__init__(init_cfg)
         if pts_bbox_head is None:
             raise TypeError('VoxelFormer needs a pts_bbox_head config')
@@ -72,6 +73,10 @@ class VoxelFormer(BaseModule):
         # row order and permutes the targets instead -- same loss, no 8-GB permute
         self.autocast_dtype = {'bf16': torch.bfloat16, 'fp16': torch.float16}.get(autocast_dtype, autocast_dtype)
         self.occupancy_rows = occupancy_rows
+        # ``device_occupancy_targets`` (ours, off by default): on the GPU the sparse occupancy annotation of the batch crosses
+        # PCIe as one asynchronous copy and becomes byte labels + the occupied count in one ``ver_occ_targets`` call
+        # (head.occupancy_targets_device) instead of a dense int64 volume filled sample by sample
+        self.device_occupancy_targets = device_occupancy_targets
         self._feature_stores = {}
         self._staging = {}                          # (6, B, 196, 768) -> (pinned host buffer, copy-done event)
 
@@ -149,7 +154,10 @@ class VoxelFormer(BaseModule):
             outs = {k: (v.float() if torch.is_tensor(v) and k != 'occupancy_preds' else v) for k, v in outs.items()}
         if self.only_det:
             return head.loss_only_detection(gt_bboxes_3d, gt_labels_3d, outs)
-        gt_occupancy = head.occupancy_targets(occ_gts, device=img_feats.device) if occ_gts else None
+        if occ_gts and self.device_occupancy_targets and img_feats.is_cuda:
+            gt_occupancy = head.occupancy_targets_device(occ_gts, rows=bool(rows), device=img_feats.device)
+        else:
+            gt_occupancy = head.occupancy_targets(occ_gts, device=img_feats.device) if occ_gts else None
         if self.only_occ:
             return head.loss_only_occupancy(gt_bboxes_3d, gt_labels_3d, gt_occupancy, outs)
         if self.add_layout:
@@ -221,7 +229,10 @@ class VoxelFormer(BaseModule):
         img_feats = self.viewpoint_features(img_metas)
         occ_gts = [np.load(m['occ_gt_path']) for m in img_metas]
         invalid = [np.load(m['occ_invalid_path']) if m.get('occ_invalid_path') else None for m in img_metas]
-        labels = head.occupancy_eval_labels(occ_gts, invalid, device=dev)
+        if self.device_occupancy_targets and dev.type == 'cuda':
+            labels = head.occupancy_targets_device(occ_gts, invalid=invalid, device=dev)
+        else:
+            labels = head.occupancy_eval_labels(occ_gts, invalid, device=dev)
         with torch.no_grad(), torch.autocast('cuda', dtype=lowp or torch.bfloat16, enabled=lowp is not None and img_feats.is_cuda):
             voxel_embed = head(img_feats, img_metas, only_bev=True)
             if self.fused_occupancy_eval if fused is None else fused:

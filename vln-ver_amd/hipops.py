@@ -958,9 +958,14 @@ def _occ_mlp_backward_fused(x2, gl, w2, w3, vec, rstd, eps, centered, gscale):
     n = x2.shape[0]
     gx = torch.empty_like(x2)
     pg = torch.empty(6 * 128 + 16 * 128 + 16 + 128 * 128, dtype=torch.float32, device=x2.device)
-    _launch('ver_occ_mlp_backward_fused', lambda: lib().ver_occ_mlp_backward_fused_stats(
+    # every workgroup's share of the parameter gradients goes to a slab of its own and the slabs are summed in a fixed order
+    # (ver_occ_mlp_backward_fused_slabs): two runs on the same inputs give the same bits, which the entries that add with
+    # float atomics do not
+    slab_bytes = lib().ver_occ_mlp_backward_fused_slab_bytes(n)
+    slabs = torch.empty(max(slab_bytes // 4, 1), dtype=torch.float32, device=x2.device)
+    _launch('ver_occ_mlp_backward_fused', lambda: lib().ver_occ_mlp_backward_fused_slabs(
         _p(x2), _p(gl), _p(w2.float().contiguous()), _p(w3.float().contiguous()), _p(vec),
-        _p(rstd), _p(gx), _p(pg), n, 128, 16, eps, _p(gscale), 2 if centered else 0, _stream()))
+        _p(rstd), _p(gx), _p(pg), _p(slabs), slab_bytes, n, 128, 16, eps, _p(gscale), 2 if centered else 0, _stream()))
     vecs = pg[:768].view(6, 128)
     dw3 = pg[768:768 + 2048].view(16, 128)
     db3 = pg[768 + 2048:768 + 2048 + 16]
@@ -1645,6 +1650,250 @@ def det_decode(cls, box, center_range, score_threshold=None, bottom_center=True,
             _p(cls), code, _p(box), ld, _p(boxes), _p(scores), _p(labels), _p(valid), _p(query), host_rng,
             float(score_threshold or 0.0), flags, bs, nq, ncls, k, codes, _stream()))
     return boxes, scores, labels, valid, query
+
+
+# ------------------------------------------------------------------------------------------
+# Occupancy targets (ver_occ_targets): the sparse (voxel, class) annotation of a batch -> byte labels + occupied counts.
+def _occ_offsets(offsets, n, name):
+    """int32 [bs + 1] offsets as numpy, checked: ascending from 0 to ``n``."""
+    import numpy as np
+    off = np.asarray(offsets)
+    if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError('%s must be an integer [bs + 1] array' % name)
+    if off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
+        raise ValueError('%s must ascend from 0 to %d' % (name, n))
+    return off.astype(np.int64)
+
+
+def occ_targets_host(pairs, offsets, voxel_num, zdim, classes, row_table=None, invalid=None, invalid_offsets=None):
+    """The contract of ``ver_occ_targets`` (include/ver_ops.h) in numpy, written from its semantics: the model the tests hold
+    the kernel to, and the CPU route of the head.  pairs int [n_total, 2] (flat voxel index, class), offsets int [bs + 1];
+    invalid int [n_invalid] with invalid_offsets [bs + 1] or None; row_table int [voxel_num / zdim, 3] or None.
+    -> (labels uint8 [bs * voxel_num], count int32 [bs + 1], bad int32 [2]).
+    Every voxel starts as ``classes``; a pair (v, c < classes) in range sets voxel v of its sample, the LARGEST class among
+    several listings; c == classes writes nothing; anything else is skipped and counted in bad[0].  bad[1]: the pairs whose
+    voxel ends up with another class than theirs.  count: the voxels that left the empty state per sample, then the total.
+    Invalid voxels become 255 after all pairs; out-of-range ones count in bad[0]."""
+    import numpy as np
+    voxel_num, zdim, classes = int(voxel_num), int(zdim), int(classes)
+    if not 1 <= classes < 255 or zdim < 1 or voxel_num < 0 or voxel_num % zdim:
+        raise ValueError('occ_targets_host: voxel_num=%d zdim=%d classes=%d (1 <= classes < 255, voxel_num %% zdim == 0)'
+                         % (voxel_num, zdim, classes))
+    pairs = np.asarray(pairs).reshape(-1, 2).astype(np.int64)
+    off = _occ_offsets(offsets, pairs.shape[0], 'offsets')
+    bs = off.size - 1
+    if bs * voxel_num >= 2 ** 31:
+        raise ValueError('occ_targets_host: %d x %d labels do not fit 2^31' % (bs, voxel_num))
+    rows = voxel_num // zdim
+    where = None
+    if row_table is not None:
+        table = np.asarray(row_table).astype(np.int64)
+        if table.shape != (rows, 3):
+            raise ValueError('occ_targets_host: row_table must be [%d, 3], got %s' % (rows, table.shape))
+        v = np.arange(voxel_num, dtype=np.int64)
+        z, q = np.divmod(v, rows)
+        # [bs, voxel_num]: byte of (sample, voxel)
+        where = ((bs * table[q, 0])[None, :] + np.arange(bs, dtype=np.int64)[:, None] * table[q, 1][None, :]
+                 + table[q, 2][None, :]) * zdim + z[None, :]
+        if bs and voxel_num and not np.array_equal(np.sort(where.reshape(-1)), np.arange(bs * voxel_num)):
+            raise ValueError('occ_targets_host: row_table is no permutation of the label bytes')
+    vol = np.full((bs, voxel_num), classes, dtype=np.uint8)
+    count = np.zeros(bs + 1, dtype=np.int32)
+    bad = np.zeros(2, dtype=np.int32)
+    for b in range(bs):
+        p = pairs[off[b]:off[b + 1]]
+        ok = (p[:, 0] >= 0) & (p[:, 0] < voxel_num) & (p[:, 1] >= 0) & (p[:, 1] <= classes)
+        bad[0] += int((~ok).sum())
+        p = p[ok & (p[:, 1] < classes)]
+        best = np.full(voxel_num, -1, dtype=np.int64)
+        np.maximum.at(best, p[:, 0], p[:, 1])
+        vol[b] = np.where(best >= 0, best, classes).astype(np.uint8)
+        count[b] = int((best >= 0).sum())
+        bad[1] += int((best[p[:, 0]] != p[:, 1]).sum())
+    count[bs] = int(count[:bs].sum())
+    if invalid is not None:
+        inv = np.asarray(invalid).reshape(-1).astype(np.int64)
+        ioff = _occ_offsets(invalid_offsets, inv.size, 'invalid_offsets')
+        if ioff.size != bs + 1:
+            raise ValueError('occ_targets_host: invalid_offsets must be [%d]' % (bs + 1))
+        for b in range(bs):
+            i = inv[ioff[b]:ioff[b + 1]]
+            ok = (i >= 0) & (i < voxel_num)
+            bad[0] += int((~ok).sum())
+            vol[b, i[ok]] = 255
+    if where is None:
+        return vol.reshape(-1), count, bad
+    labels = np.empty(bs * voxel_num, dtype=np.uint8)
+    labels[where.reshape(-1)] = vol.reshape(-1)
+    return labels, count, bad
+
+
+class PackedOccGts:
+    """The occupancy annotation of a batch in ONE int32 buffer, ``[offsets (bs + 1) | invalid_offsets (bs + 1) | pairs
+    (2 n_total) | invalid (n_invalid)]``, so that one copy moves all of it (``pack_occ_gts``).  ``pairs``, ``offsets``,
+    ``invalid`` and ``invalid_offsets`` are views of ``buffer``; ``to(device)`` is that copy."""
+
+    def __init__(self, buffer, bs, n_total, n_invalid, has_invalid, slot=None):
+        self.buffer, self.bs, self.n_total, self.n_invalid, self.has_invalid = buffer, bs, n_total, n_invalid, has_invalid
+        self._slot, self._generation = slot, (slot[2] if slot is not None else None)
+        h = 2 * (bs + 1)
+        self.offsets = buffer[:bs + 1]
+        self.invalid_offsets = buffer[bs + 1:h] if has_invalid else None
+        self.pairs = buffer[h:h + 2 * n_total].view(n_total, 2)
+        self.invalid = buffer[h + 2 * n_total:h + 2 * n_total + n_invalid] if has_invalid else None
+
+    def to(self, device):
+        """On ``device``: one asynchronous copy on the current stream out of the (pinned) staging buffer, whose next
+        ``pack_occ_gts`` waits for this copy's event before it rewrites the buffer."""
+        device = torch.device(device)
+        if self._slot is not None and self._slot[2] != self._generation:
+            raise RuntimeError('PackedOccGts.to: the staging buffer of this size class was packed again since -- one pack is '
+                               'outstanding per size class: copy it (.to) before the next pack_occ_gts, or pack with pinned=False')
+        if device.type != 'cuda':
+            return PackedOccGts(self.buffer.clone(), self.bs, self.n_total, self.n_invalid, self.has_invalid)
+        dev = self.buffer.to(device, non_blocking=True)
+        if self._slot is not None:
+            done = torch.cuda.Event()
+            done.record()
+            self._slot[1] = done
+        return PackedOccGts(dev, self.bs, self.n_total, self.n_invalid, self.has_invalid)
+
+
+_OCC_STAGING = {}            # capacity in int32 elements (a power of two) -> [pinned host buffer, copy-done event or None, packs]
+
+
+def pack_occ_gts(occ_gts, invalid=None, pinned=True):
+    """Host half of ``occ_targets``: ``occ_gts[b]`` -- an integer [n, 2] array of (flat voxel index, class) pairs, or the
+    reference's one-element list around it (``occ_gts[b][0]``) -- and optionally ``invalid[b]`` (integer voxel indices or
+    None) of every sample, concatenated into one int32 staging buffer with their offsets -> ``PackedOccGts`` on the host.
+    With ``pinned`` and a GPU present the buffer is pinned, kept per size class (the next power of two) and reused: its
+    ``to(device)`` is ONE ``non_blocking`` copy, and the buffer is not rewritten before that copy's event has completed.
+    A loader that wants the copy to overlap the previous step calls this and ``.to(device)`` ahead of time and hands the
+    result to ``head.occupancy_targets_device``.  ONE pack is outstanding per size class: the next ``pack_occ_gts`` of that
+    class rewrites the buffer, and ``to`` of the earlier object then raises instead of copying the other batch
+    (``pinned=False`` gives an object with memory of its own).  Values outside int32 are saturated, so they stay out of range."""
+    import numpy as np
+
+    def arr(a, cols):
+        if cols == 2 and isinstance(a, (list, tuple)):
+            a = a[0]                                           # occ_gts[bs][queue_index], as head.occupancy_targets reads it
+        if a is None:
+            return np.zeros((0, 2) if cols == 2 else (0,), dtype=np.int32)
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if a.size == 0:
+            return np.zeros((0, 2) if cols == 2 else (0,), dtype=np.int32)
+        if not np.issubdtype(a.dtype, np.integer):
+            raise TypeError('pack_occ_gts: integer arrays expected, got %s' % a.dtype)
+        if cols == 2 and (a.ndim != 2 or a.shape[1] != 2):
+            raise ValueError('pack_occ_gts: a sample is [n, 2] (voxel index, class) pairs, got %s' % (a.shape,))
+        return a if cols == 2 else a.reshape(-1)
+
+    gts = [arr(a, 2) for a in occ_gts]
+    bs = len(gts)
+    has_invalid = invalid is not None
+    inv = [arr(a, 1) for a in invalid] if has_invalid else []
+    if has_invalid and len(inv) != bs:
+        raise ValueError('pack_occ_gts: %d invalid lists for %d samples' % (len(inv), bs))
+    n_total, n_invalid = sum(a.shape[0] for a in gts), sum(a.size for a in inv)
+    used = 2 * (bs + 1) + 2 * n_total + n_invalid
+    if max(n_total, n_invalid) >= 2 ** 31 - 1 or used >= 2 ** 31:
+        raise ValueError('pack_occ_gts: %d pairs / %d invalid voxels exceed the int32 offsets' % (n_total, n_invalid))
+    slot = None
+    if pinned and torch.cuda.is_available():
+        cap = 1024
+        while cap < used:
+            cap *= 2
+        slot = _OCC_STAGING.get(cap)
+        if slot is None:
+            slot = _OCC_STAGING[cap] = [torch.empty(cap, dtype=torch.int32, pin_memory=True), None, 0]
+        elif slot[1] is not None:
+            slot[1].synchronize()                              # the previous copy out of this buffer
+        slot[2] += 1                                           # (an earlier pack of this size class is void from here on)
+        host = slot[0][:used]
+    else:
+        host = torch.empty(used, dtype=torch.int32)
+    hv = host.numpy()
+    lim = np.iinfo(np.int32)
+
+    def put(dst, a):
+        if a.dtype.itemsize > 4 or a.dtype == np.uint32:
+            np.clip(a, lim.min, lim.max, out=dst, casting='unsafe')
+        else:
+            dst[...] = a
+
+    h = 2 * (bs + 1)
+    hv[0] = 0
+    hv[bs + 1] = 0
+    if bs:
+        hv[1:bs + 1] = np.cumsum([a.shape[0] for a in gts])
+        hv[bs + 2:h] = np.cumsum([a.size for a in inv]) if has_invalid else 0
+    pos = h
+    for a in gts:
+        put(hv[pos:pos + a.size].reshape(-1, 2), a)
+        pos += a.size
+    for a in inv:
+        put(hv[pos:pos + a.size], a)
+        pos += a.size
+    return PackedOccGts(host, bs, n_total, n_invalid, has_invalid, slot)
+
+
+def occ_targets(pairs, offsets, voxel_num, zdim, classes, row_table=None, invalid=None, invalid_offsets=None, out=None):
+    """Byte labels and occupied counts of a batch from its sparse annotation (ver_occ_targets): pairs int32 | int64
+    [n_total, 2] (flat voxel index, class) of all samples, offsets int32 [bs + 1], both on the GPU; ``row_table`` int32
+    [voxel_num / zdim, 3] (``occ_proj_lattice.row_table``) writes the labels in the group-major row order of the occupancy
+    GEMMs, None in the reference's voxel order; ``invalid`` int32 | int64 [n_invalid] with ``invalid_offsets`` int32
+    [bs + 1]: voxels set to 255 after the pairs.  ``out``: ``(labels, count, bad)`` of an earlier call to write into.
+    -> (labels uint8 [bs * voxel_num], count int32 [bs + 1], bad int32 [2]); semantics: ``occ_targets_host``.
+    Four launches at most, no host synchronisation, capturable."""
+    what = 'occ_targets'
+    pairs = _gpu(pairs, 'pairs')
+    dev = pairs.device
+    if pairs.dtype not in (torch.int32, torch.int64) or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise TypeError('%s: pairs must be int32 or int64 [n_total, 2], got %s %s' % (what, pairs.dtype, tuple(pairs.shape)))
+
+    def idx(t, name, shape):
+        t = _gpu(t, name, torch.int32)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise ValueError('%s: %s must be int32 %s on %s, got %s on %s' % (what, name, shape, dev, tuple(t.shape), t.device))
+        return t
+
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError('%s: offsets must be [bs + 1]' % what)
+    bs = offsets.numel() - 1
+    offsets = idx(offsets, 'offsets', (bs + 1,))
+    voxel_num, zdim, classes = int(voxel_num), int(zdim), int(classes)
+    if voxel_num < 0 or zdim < 1 or classes < 1:
+        raise ValueError('%s: voxel_num=%d zdim=%d classes=%d' % (what, voxel_num, zdim, classes))
+    if row_table is not None:
+        row_table = idx(row_table, 'row_table', (voxel_num // zdim, 3))
+    n_invalid = 0
+    if (invalid is None) != (invalid_offsets is None):
+        raise ValueError('%s: invalid and invalid_offsets come together' % what)
+    if invalid is not None:
+        invalid = _gpu(invalid, 'invalid')
+        if invalid.dtype not in (torch.int32, torch.int64) or invalid.dim() != 1 or invalid.device != dev:
+            raise TypeError('%s: invalid must be int32 or int64 [n_invalid] on %s' % (what, dev))
+        invalid_offsets = idx(invalid_offsets, 'invalid_offsets', (bs + 1,))
+        n_invalid = invalid.numel()
+    total = bs * voxel_num
+    padded = (total + 3) // 4 * 4
+    if out is None:
+        labels = torch.empty(padded, dtype=torch.uint8, device=dev)[:total]
+        count = torch.empty(bs + 1, dtype=torch.int32, device=dev)
+        bad = torch.empty(2, dtype=torch.int32, device=dev)
+    else:
+        labels, count, bad = out
+        room = labels.untyped_storage().nbytes() - labels.storage_offset()
+        if (labels.dtype != torch.uint8 or labels.numel() != total or not labels.is_contiguous() or labels.device != dev
+                or room < padded):
+            raise ValueError('%s: out labels must be %d contiguous uint8 on %s, allocated up to a multiple of 4 bytes' % (what, total, dev))
+        labels = labels.view(-1)
+        count, bad = idx(count, 'out count', (bs + 1,)), idx(bad, 'out bad', (2,))
+    code = lambda t: 1 if t is not None and t.dtype == torch.int64 else 0
+    _launch('ver_occ_targets', lambda: lib().ver_occ_targets(
+        _p(pairs), code(pairs), _p(offsets), pairs.shape[0], _p(invalid), code(invalid), _p(invalid_offsets), n_invalid,
+        _p(row_table), _p(labels), _p(count), _p(bad), voxel_num, zdim, classes, bs, _stream()))
+    return labels, count, bad
 
 
 # ------------------------------------------------------------------------------------------
