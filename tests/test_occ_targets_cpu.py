@@ -1,6 +1,7 @@
 """Occupancy targets from the sparse annotation, without a GPU: the numpy model of ``ver_occ_targets``
 (``hipops.occ_targets_host``) against the head's dense ``occupancy_targets`` / ``occupancy_eval_labels`` and the plan's row
-maps, the stated rules for repeated and rejected pairs, the host packer, the row table and the argument checks of the C ABI."""
+maps, the stated rules for repeated and rejected pairs, the host packer, the row table, the argument checks of the C ABI, and
+the labels module's ``(gt, avg)`` of the occupancy loss for both label forms (``dense_heads/occupancy_labels.py``)."""
 import ctypes
 import types
 
@@ -254,6 +255,57 @@ def test_targets_object_converts_between_the_orders(plan):
         lost.check()
     with pytest.raises(ValueError):
         OT(vox.labels, vox.count, vox.bad, 'rows', bs, None, Z)
+
+
+def test_loss_labels_of_a_dense_tensor_and_of_targets_are_the_same_pairs(plan):
+    """``occupancy_labels.loss_labels``, the one place where the occupancy loss gets ``(gt, avg)``: the dense int64 tensor
+    and the ``OccupancyTargets`` of the same sparse pairs give identical bytes in identical positions and equal counts, for
+    logits in the voxel order and in the plan's row order; the count of a mask whose length is no multiple of 8 (the
+    ``.sum()`` branch) equals the word-sum count of the same labels padded with empty ones; -1 and 300 leave the narrowing
+    step as 255."""
+    hip, opl, ol = pkg('hipops'), pkg('dense_heads.occ_proj_lattice'), pkg('dense_heads.occupancy_labels')
+    Head = pkg('dense_heads.voxelformer_occupancy_head').VoxelFormerOccupancyHead
+    bs, Z = 2, 5
+    voxel_num = ROWS * Z
+    gts = _annotation(np.random.default_rng(9), bs, voxel_num)
+    dense = Head.occupancy_targets(_head_stub(voxel_num), gts)
+    pairs, off = _flat(gts)
+    vox = ol.OccupancyTargets(*(T(a) for a in hip.occ_targets_host(pairs, off, voxel_num, Z, CLASSES)), 'voxels', bs, None, Z)
+    row = ol.OccupancyTargets(*(T(a) for a in hip.occ_targets_host(pairs, off, voxel_num, Z, CLASSES, row_table=opl.row_table(plan))),
+                              'rows', bs, plan, Z)
+    in_rows = opl.voxels_to_rows(dense.reshape(bs, Z, plan.rows).permute(0, 2, 1), plan, bs).reshape(-1)
+    assert not torch.equal(in_rows, dense.reshape(-1))
+    for logit_plan, want in ((None, dense.reshape(-1)), (plan, in_rows)):
+        for as_bytes in (False, True):
+            gt, avg = ol.loss_labels(dense, CLASSES, logit_plan, bs, Z, as_bytes=as_bytes)
+            assert gt.dtype == torch.int64 and torch.equal(gt, want)           # (a CPU tensor is never narrowed)
+            assert avg.dtype == torch.float32 and float(avg) == len(pairs)
+            for targets in (vox, row):
+                got, count = ol.loss_labels(targets, CLASSES, logit_plan, bs, Z, as_bytes=as_bytes)
+                assert got.dtype == (torch.uint8 if as_bytes else torch.int64) and got.shape == want.shape
+                assert torch.equal(got.to(torch.uint8), want.to(torch.uint8))
+                assert count.dtype == torch.float32 and float(count) == float(avg)
+    assert torch.equal(ol.labels_in_rows(row, plan, bs, Z), ol.labels_in_rows(dense, plan, bs, Z, dtype=torch.uint8))
+    assert ol.labels_in_voxels(dense) is dense and ol.labels_in_voxels(vox) is vox.labels
+    # the count: 19197 labels take the plain sum, the same labels padded with three empty ones the word sum
+    cut = in_rows[:bs * voxel_num - 3].to(torch.uint8)
+    padded = torch.cat([cut, torch.full((3,), CLASSES, dtype=torch.uint8)])
+    assert cut.numel() % 8 == 5 and padded.numel() % 8 == 0
+    short, long_ = ol.count_occupied(cut < CLASSES), ol.count_occupied(padded < CLASSES)
+    assert float(short) == float(long_) == float(ol.count_occupied(padded < CLASSES, by_words=False)) == int((cut < CLASSES).sum())
+    assert 0 < float(short) < len(pairs) + 1 and short.dtype == long_.dtype == torch.float32
+    # the narrowing step, forced on a CPU tensor: out-of-range labels stay out of range as bytes
+    odd = torch.tensor([-1, 300, 0, CLASSES, 255, 256, -7, 2 ** 40, 254])
+    assert ol.narrow_labels(odd).tolist() == [255, 255, 0, CLASSES, 255, 255, 255, 255, 254]
+    spoiled = dense.clone()
+    spoiled[0, 17], spoiled[1, 4321] = -1, 300
+    narrowed = ol.narrow_labels(spoiled)
+    assert narrowed.dtype == torch.uint8 and narrowed[0, 17] == 255 and narrowed[1, 4321] == 255
+    keep = torch.ones_like(spoiled, dtype=torch.bool)
+    keep[0, 17] = keep[1, 4321] = False
+    assert torch.equal(narrowed[keep], dense[keep].to(torch.uint8))
+    through = ol.labels_in_rows(narrowed, plan, bs, Z).reshape(-1)
+    assert int((through == 255).sum()) == 2 and int((through != in_rows.to(torch.uint8)).sum()) == 2
 
 
 def test_reproducible_mlp_backward_entry_without_a_gpu():

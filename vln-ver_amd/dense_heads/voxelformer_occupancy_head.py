@@ -29,7 +29,8 @@ from . import coders, losses  # noqa: F401  (registers NMSFreeCoder / FocalLoss 
 from .assigner import SamplingResult, build_assigner
 from .coders import normalize_bbox
 from ..ddp import reduce_mean
-from .occ_proj_lattice import lattice_plan, occ_proj_from_lattice, row_table, rows_to_voxels, voxels_to_rows
+from .occ_proj_lattice import lattice_plan, occ_proj_from_lattice, row_table, rows_to_voxels
+from .occupancy_labels import OccupancyTargets, classify, dense_labels, labels_in_rows, labels_in_voxels, loss_labels
 from .row_linear import row_linear
 from .upsample import full_volume, is_reference_geometry, upsample_lattice
 
@@ -47,47 +48,6 @@ def _mean_over_ranks(value, like):
 # Ground truth of a batch in static shapes (``VoxelFormerOccupancyHead.pad_gts``), all on the device: boxes [bs, cap, 9]
 # (gravity centre, dims, yaw, zero velocity; rows >= counts[b] are padding), labels int64 [bs, cap], counts int32 [bs].
 PaddedGts = collections.namedtuple('PaddedGts', 'boxes labels counts')
-
-
-class OccupancyTargets:
-    """Occupancy targets of a batch in static shapes, as ``VoxelFormerOccupancyHead.occupancy_targets_device`` builds them
-    from the sparse annotation in one launch sequence (``hipops.occ_targets``); accepted wherever the dense ``[bs,
-    voxel_num]`` tensor is.  ``labels`` uint8 [bs * voxel_num]: ``classes`` = empty, 255 = not evaluated; ``order`` says where
-    a voxel's byte sits: ``'voxels'`` = the reference's (Z, X, Y) order per sample, ``'rows'`` = the group-major row order
-    of the occupancy GEMMs of ``plan`` (the bytes the loss kernels read next to the logit rows, as they are).  ``count``
-    int32 [bs + 1]: occupied voxels per sample and their total (``count[-1]`` is the losses' ``avg_factor``); ``bad`` int32
-    [2]: rejected pairs, and listings of a voxel that lost to a larger class."""
-
-    def __init__(self, labels, count, bad, order, bs, plan=None, zdim=1):
-        if order not in ('rows', 'voxels') or (order == 'rows' and plan is None):
-            raise ValueError("OccupancyTargets: order is 'voxels', or 'rows' with the plan the rows belong to")
-        self.labels, self.count, self.bad, self.order, self.bs, self.plan, self.zdim = labels, count, bad, order, bs, plan, zdim
-
-    def check(self):
-        """Read ``bad`` on the host (a device -> host synchronisation) and raise ``ValueError`` when a counter is set."""
-        rejected, lost = (int(v) for v in self.bad.tolist())
-        if rejected or lost:
-            what = []
-            if rejected:
-                what.append('bad[0] = %d: pairs or invalid voxels with an index or a class out of range were skipped '
-                            '(the reference raises on them)' % rejected)
-            if lost:
-                what.append('bad[1] = %d: listings of a voxel that lost to a larger class of the same voxel' % lost)
-            raise ValueError('occupancy annotation: ' + '; '.join(what))
-        return self
-
-    def ordered(self, order, plan=None):
-        """``labels`` (uint8 [bs * voxel_num]) in ``order``: as they are when that is their order, else permuted once with
-        the plan's row maps -- the only place where targets of this kind change their order."""
-        if order == self.order and (order == 'voxels' or plan is self.plan):
-            return self.labels
-        z = self.zdim
-        voxels = self.labels
-        if self.order == 'rows':
-            voxels = rows_to_voxels(self.labels.view(-1, z), self.plan, self.bs).permute(0, 2, 1).reshape(-1)
-        if order == 'voxels':
-            return voxels
-        return voxels_to_rows(voxels.view(self.bs, z, plan.rows).permute(0, 2, 1), plan, self.bs).reshape(-1)
 
 
 def _to_device_async(t, dev):
@@ -111,12 +71,11 @@ def _confusion(logits, labels, samples, thresholds, hist):
         from ..hipops import occ_confusion
         return occ_confusion(logits, labels.to(torch.uint8), thresholds, samples, hist)
     k = c + 1
-    p = logits.float().sigmoid()
     gt = labels.long().view(samples, -1)
     keep = gt < k
     first = torch.arange(samples, device=gt.device)[:, None] * k + gt           # (sample, label) row of the histogram
     for t, thr in enumerate(thresholds):
-        pred = torch.cat((p, torch.full_like(p[:, :1], thr)), dim=-1).argmax(dim=-1).view(samples, -1)
+        pred = classify(logits, thr).view(samples, -1)
         counts = torch.bincount((first * k + pred)[keep], minlength=samples * k * k)
         hist[:, t] += counts.view(samples, k, k).to(hist.device)
     return hist
@@ -428,14 +387,18 @@ class VoxelFormerOccupancyHead(BaseModule):
         else:
             x = voxel_embed.view(bs, self.bev_z, self.bev_h, self.bev_w, c)
             ox, oy = self.bev_h, self.bev_w
+        return self._occ_from_grid(x, bs, ox, oy)
+
+    def _occ_from_grid(self, x, bs, ox, oy):
+        """``occ_proj`` + ``occ_branches`` on a [bs, bev_z, ox, oy, C] view (head:566-580, :338-350) -> logits
+        [bs, ox*oy*occ_zdim, classes] in the reference's (Z, X, Y) order."""
         if self.bev_z == self.occ_zdim:
             occ = self.occ_proj(x)
         else:
             x = x.permute(0, 2, 3, 1, 4).flatten(3)
             occ = self.occ_proj(x)
             occ = occ.view(bs, ox, oy, self.occ_zdim, self.occ_dims).permute(0, 3, 1, 2, 4)
-        occ = occ.reshape(bs, -1, self.occ_dims)
-        return self._occ_mlp(occ)
+        return self._occ_mlp(occ.reshape(bs, -1, self.occ_dims))
 
     @staticmethod
     def _occ_mlp_is_fusable(mods):
@@ -459,6 +422,13 @@ class VoxelFormerOccupancyHead(BaseModule):
         features without changing LayerNorm(W x + b)."""
         return weight - weight.mean(0, keepdim=True), bias - bias.mean()
 
+    def _centered_second_linear(self):
+        """``_centered`` (W2, b2) of ``occ_branches[3]`` in fp32, whatever the autocast state: what the fused MLP kernels
+        take with ``centered=True`` after a folded, centred first Linear."""
+        l2 = self.occ_branches[3]
+        with torch.autocast('cuda', enabled=False):
+            return self._centered(l2.weight.float(), l2.bias.float())
+
     def _occ_mlp_runs_fused(self, x):
         """True when ``_occ_mlp`` will take the fused MFMA kernels for this input (bf16 arithmetic)."""
         return x.is_cuda and self._occ_mlp_is_fusable(list(self.occ_branches)) and (
@@ -470,38 +440,15 @@ class VoxelFormerOccupancyHead(BaseModule):
         Function: x [N, 128] rows in GEMM order, gt_occupancy in the reference's (Z, X, Y) voxel order.  ``class_weight``:
         the table of ``class_weight_table`` -- indexed by label VALUE, so the row permutation of the labels leaves it alone."""
         from ..hipops import occ_mlp_focal_loss_sum
-        _, n1, _, l2, n2, _, l3 = list(self.occ_branches)
+        _, n1, _, _, n2, _, l3 = list(self.occ_branches)
         lo = self.loss_occupancy
-        if isinstance(gt_occupancy, OccupancyTargets):
-            # byte labels already in the rows' order and the occupied count: nothing to clamp, narrow, permute or reduce
-            gt, avg = gt_occupancy.ordered('rows', plan), gt_occupancy.count[-1] * 1.0
-            with torch.autocast('cuda', enabled=False):
-                w2c, b2c = self._centered(l2.weight.float(), l2.bias.float())
-                s = occ_mlp_focal_loss_sum(x.to(torch.bfloat16), n1.weight, n1.bias, w2c, b2c, n2.weight, n2.bias,
-                                           l3.weight, l3.bias, gt, n1.eps, lo.gamma, lo.alpha, centered=True,
-                                           class_weight=class_weight)
-            return torch.nan_to_num(lo.loss_weight * (s / avg))
-        lo.check_label_range(gt_occupancy, self.occupancy_classes)      # (the same first-call host check as FocalLoss.forward)
-        # the labels are permuted into the GEMMs' row order and counted as BYTES (17 classes): int64 labels made the
-        # permutation and the count three passes over 0.77 GB each at 192 viewpoints (1.4 ms; now 0.3 with the narrowing copy).
-        # The host-side range check above only runs on a module's first call: labels are clamped into [-1, 255] before the
-        # narrowing cast, so that an out-of-range value stays out of range as a byte (-1 -> 255, >= 256 -> 255: both reach
-        # the kernel's own check as invalid labels) instead of wrapping into a valid class.
-        narrow = gt_occupancy.is_cuda and gt_occupancy.dtype == torch.int64 and self.occupancy_classes < 255
-        gt = gt_occupancy.clamp(-1, 255).to(torch.uint8) if narrow else gt_occupancy
-        gt = gt.reshape(bs, self.occ_zdim, plan.rows).permute(0, 2, 1)                # -> [bs, X*Y, Z]
-        gt = voxels_to_rows(gt, plan, bs).reshape(-1)
-        occupied = gt < self.occupancy_classes
-        if narrow and occupied.numel() % 8 == 0:
-            # the count of a 0/1 byte mask, eight bytes at a time: (word * 0x0101...01) >> 56 is the sum of the word's bytes
-            # (exact; the reduction kernel reads a bool tensor one byte per lane: 0.46 ms for 97 M labels against 0.05)
-            words = occupied.view(torch.uint8).view(torch.int64)
-            avg = ((words * 0x0101010101010101) >> 56).sum() * 1.0
-        else:
-            avg = occupied.sum() * 1.0
-        # (the byte labels go to the kernel as they are: ver_focal_loss_forward_grad_u8)
+        if torch.is_tensor(gt_occupancy):
+            # (the same first-call host check as FocalLoss.forward; it only runs on a module's first call, so the labels are
+            #  clamped before they are narrowed to bytes all the same: occupancy_labels.narrow_labels)
+            lo.check_label_range(gt_occupancy, self.occupancy_classes)
+        gt, avg = loss_labels(gt_occupancy, self.occupancy_classes, plan, bs, self.occ_zdim, as_bytes=True)
+        w2c, b2c = self._centered_second_linear()
         with torch.autocast('cuda', enabled=False):
-            w2c, b2c = self._centered(l2.weight.float(), l2.bias.float())
             s = occ_mlp_focal_loss_sum(x.to(torch.bfloat16), n1.weight, n1.bias, w2c, b2c, n2.weight, n2.bias,
                                        l3.weight, l3.bias, gt, n1.eps, lo.gamma, lo.alpha, centered=True,
                                        class_weight=class_weight)
@@ -520,7 +467,7 @@ class VoxelFormerOccupancyHead(BaseModule):
             l1, n1, _, l2, n2, _, l3 = mods
             with torch.autocast('cuda', enabled=False):
                 if first_folded:                 # the caller centred Linear 1 in the fold; Linear 2 here
-                    w2c, b2c = self._centered(l2.weight.float(), l2.bias.float())
+                    w2c, b2c = self._centered_second_linear()
                     return occ_mlp(x.to(torch.bfloat16), None, None, n1.weight, n1.bias, w2c, b2c,
                                    n2.weight, n2.bias, l3.weight, l3.bias, n1.eps, centered=True)
                 return occ_mlp(x.to(torch.bfloat16), l1.weight, l1.bias, n1.weight, n1.bias, l2.weight, l2.bias,
@@ -692,54 +639,27 @@ class VoxelFormerOccupancyHead(BaseModule):
 
     def _only_occ(self, voxel_embed):
         """head:338-350: the only_occ branch never upsamples (plain [bs,Z,H,W,C] view)."""
-        bs, c = voxel_embed.shape[0], self.embed_dims
-        x = voxel_embed.reshape(bs, self.bev_z, self.bev_h, self.bev_w, c)
-        if self.bev_z == self.occ_zdim:
-            occ = self.occ_proj(x)
-        else:
-            x = x.permute(0, 2, 3, 1, 4).flatten(3)
-            occ = self.occ_proj(x)
-            occ = occ.view(bs, self.bev_h, self.bev_w, self.occ_zdim, self.occ_dims)
-            occ = occ.permute(0, 3, 1, 2, 4)
-        return self._occ_mlp(occ.reshape(bs, -1, self.occ_dims))
+        bs = voxel_embed.shape[0]
+        x = voxel_embed.reshape(bs, self.bev_z, self.bev_h, self.bev_w, self.embed_dims)
+        return self._occ_from_grid(x, bs, self.bev_h, self.bev_w)
 
     def occupancy_loss(self, occupancy_preds, gt_occupancy, class_weights=None):
         """Occupancy term of ``loss_single`` (head:977-989): sigmoid focal loss over
         [N, classes] logits with integer targets in [0, classes] (``classes`` = empty voxel),
         normalised by the number of occupied voxels, NaN-guarded.  ``class_weights`` (``class_weight_table``): every row
         times the factor of its label, as ``loss_only_occupancy`` does with ``occ_weights`` (head:1417-1425); the
-        normaliser stays the unweighted count."""
-        if isinstance(gt_occupancy, OccupancyTargets):
-            return self._occupancy_loss_of_targets(occupancy_preds, gt_occupancy, class_weights)
+        normaliser stays the unweighted count.
+        An ``OccupancyTargets`` brings its labels in the order of the logits and ``count[-1]`` as the normaliser: no
+        compare, no reduction over the labels."""
+        plan = bs = None
         if isinstance(occupancy_preds, tuple):                         # (logits in GEMM row order, plan, bs)
             occupancy_preds, plan, bs = occupancy_preds               # [bs*X*Y, Z, classes], group-major rows
-            gt = gt_occupancy.reshape(bs, self.occ_zdim, plan.rows).permute(0, 2, 1)   # (Z, X, Y) order -> [bs, X*Y, Z]
-            gt_occupancy = voxels_to_rows(gt, plan, bs)
         preds = occupancy_preds.reshape(-1, self.occupancy_classes)
         if not (preds.is_cuda and preds.dtype == torch.bfloat16):     # the fused loss reads bf16 as is
             preds = preds.float()
-        gt = gt_occupancy.reshape(-1)
-        avg = (gt < self.occupancy_classes).sum() * 1.0
+        gt, avg = loss_labels(gt_occupancy, self.occupancy_classes, plan, bs, self.occ_zdim)
+        gt, avg = gt.to(preds.device), avg.to(preds.device)
         table = self.class_weight_table(class_weights, preds.device)
-        if table is None:
-            return torch.nan_to_num(self.loss_occupancy(preds, gt, avg_factor=avg))
-        return torch.nan_to_num(self.loss_occupancy(preds, gt, avg_factor=avg, class_weight=table))
-
-    def _occupancy_loss_of_targets(self, occupancy_preds, targets, class_weights=None):
-        """``occupancy_loss`` against an ``OccupancyTargets``: its labels in the order of the logits (the row order for the
-        row-order tuple) and ``count[-1]`` as the normaliser -- no compare, no reduction over the labels.  The registered
-        loss takes int64 targets (``ver_focal_loss_forward``, ``F.one_hot``): the bytes are widened here."""
-        if isinstance(occupancy_preds, tuple):                         # (logits in GEMM row order, plan, bs)
-            occupancy_preds, plan, _ = occupancy_preds
-            gt = targets.ordered('rows', plan)
-        else:
-            gt = targets.ordered('voxels')
-        preds = occupancy_preds.reshape(-1, self.occupancy_classes)
-        if not (preds.is_cuda and preds.dtype == torch.bfloat16):     # the fused loss reads bf16 as is
-            preds = preds.float()
-        avg = targets.count[-1].to(preds.device) * 1.0
-        table = self.class_weight_table(class_weights, preds.device)
-        gt = gt.to(preds.device).long()
         if table is None:
             return torch.nan_to_num(self.loss_occupancy(preds, gt, avg_factor=avg))
         return torch.nan_to_num(self.loss_occupancy(preds, gt, avg_factor=avg, class_weight=table))
@@ -790,11 +710,12 @@ class VoxelFormerOccupancyHead(BaseModule):
         bbox_weights = bbox_weights * self.code_weights
         loss_bbox = self.loss_bbox(bbox_preds[isnotnan, :10], normalized[isnotnan, :10],
                                    bbox_weights[isnotnan, :10], avg_factor=num_total_pos)
-        if occupancy_preds is not None:
-            loss_occ = self.occupancy_loss(occupancy_preds, gt_occupancy)
-        else:
-            loss_occ = torch.zeros_like(loss_cls)
+        loss_occ = self._occupancy_term(occupancy_preds, gt_occupancy, loss_cls)
         return torch.nan_to_num(loss_cls), torch.nan_to_num(loss_bbox), loss_occ
+
+    def _occupancy_term(self, occupancy_preds, gt_occupancy, like):
+        """``occupancy_loss`` without class weights, or a zero like ``like`` for a head that predicted no occupancy."""
+        return self.occupancy_loss(occupancy_preds, gt_occupancy) if occupancy_preds is not None else torch.zeros_like(like)
 
     def loss(self, gt_bboxes_list, gt_labels_list, gt_occupancy, preds_dicts):
         """Loss dict of the reference (head:1251-1384): last decoder layer -> ``loss_cls``,
@@ -805,56 +726,66 @@ class VoxelFormerOccupancyHead(BaseModule):
         ``gt_labels_list`` is then unused): the static-shape form, with which nothing between the predictions and the loss
         dict touches the host; the two lists are padded here otherwise.  ``'fused'`` forms costs, targets, losses and their
         gradients in the set-loss kernels (``_set_loss_fused``) instead of the torch chain."""
-        all_cls, all_box = preds_dicts['all_cls_scores'], preds_dicts['all_bbox_preds']
         occ = preds_dicts['occupancy_preds']
-        nl = len(all_cls)
-        losses = {}
-        pending = preds_dicts.get('pending_targets')
-        padded = labels = targets = per_layer = None        # per_layer: (loss_cls, loss_bbox) of every decoder layer
-        if isinstance(gt_bboxes_list, PaddedGts) or self._device_solver():
-            if not self._device_solver():
-                raise ValueError("loss: a PaddedGts needs train_cfg.assigner.solver = 'device'")
-            gts = gt_bboxes_list if isinstance(gt_bboxes_list, PaddedGts) else self.pad_gts(gt_bboxes_list, gt_labels_list)
+        terms, lo = self._detection_terms(preds_dicts['all_cls_scores'], preds_dicts['all_bbox_preds'], gt_bboxes_list,
+                                          gt_labels_list, pending=preds_dicts.get('pending_targets'), occ=occ,
+                                          gt_occupancy=gt_occupancy,
+                                          padded_error="loss: a PaddedGts needs train_cfg.assigner.solver = 'device'")
+        if lo is None:
+            lo = self._occupancy_term(occ, gt_occupancy, terms[-1][0])
+        return self._loss_dict(terms, loss_occupancy=lo, loss_flow=torch.zeros_like(terms[-1][0]))
+
+    def _detection_terms(self, all_cls, all_box, gts, gt_labels, pending=None, batched=True, padded_error=None, occ=None,
+                         gt_occupancy=None):
+        """``(loss_cls, loss_bbox)`` of every decoder layer, by the one route the assigner's solver and the form of the
+        ground truth select -> (list of L pairs, occupancy term or None).  ``gts``: per-sample boxes or a ``PaddedGts``
+        (``gt_labels`` is then unused; ``padded_error``: what the ``ValueError`` says when the solver cannot take one).
+        * solver 'fused': the set-loss kernels (``_set_loss_fused``);
+        * solver 'device' (``batched`` only): the torch chain on targets solved on the device (``_targets_device``);
+        * ``pending``: targets ``forward`` started for these very box tensors (``_targets_finish``);
+        * ``batched``: all layers and samples in one round trip to the host solver (``_batched_targets``);
+        * else, or when there was nothing to batch: ``loss_single`` per layer, whose last call also evaluates the occupancy
+          term of ``occ`` -- the only route that returns one.
+        ``batched=False`` (``loss_only_detection``, ``loss_addlayout``): 'fused' or ``loss_single``, nothing in between."""
+        on_device = self._device_solver() if batched else self._fused_solver()
+        targets = None
+        if isinstance(gts, PaddedGts) or on_device:
+            if not on_device:
+                raise ValueError(padded_error)
+            if not isinstance(gts, PaddedGts):
+                gts = self.pad_gts(gts, gt_labels)
             if self._fused_solver():
-                per_layer = self._set_loss_fused(all_cls, all_box, gts, self.loss_bbox)
-            else:
-                targets = self._targets_device(all_cls, all_box, gts)
-        elif pending is not None and pending.get('key') == tuple(id(g) for g in gt_bboxes_list):
+                return list(zip(*self._set_loss_fused(all_cls, all_box, gts, self.loss_bbox))), None
+            targets = self._targets_device(all_cls, all_box, gts)
+        elif batched and pending is not None and pending.get('key') == tuple(id(g) for g in gts):
             targets = self._targets_finish(pending)         # started in forward(), solved under the occupancy head
-        else:
-            padded, labels = self._prepare_gts(gt_bboxes_list, gt_labels_list, all_box.device)
-            targets = self._batched_targets(all_cls, all_box, padded, labels)
-        if per_layer is None and targets is not None:
+        elif batched:
+            targets = self._batched_targets(all_cls, all_box, *self._prepare_gts(gts, gt_labels, all_box.device))
+        if targets is not None:
             # every decoder layer's classification / box terms in one pass over [L * bs * Nq] rows
-            per_layer = self._losses_from_targets(all_cls, all_box, *targets)
-        if per_layer is None and padded is None:
-            padded, labels = self._prepare_gts(gt_bboxes_list, gt_labels_list, all_box.device)
-        for lvl in range(nl):
-            last = lvl == nl - 1
-            if per_layer is None:
-                lc, lb, lo = self.loss_single(all_cls[lvl], all_box[lvl], occ if last else None, padded, labels,
-                                              gt_occupancy if last else None)
-            else:
-                lc, lb = per_layer[0][lvl], per_layer[1][lvl]
-                lo = self.occupancy_loss(occ, gt_occupancy) if (last and occ is not None) else torch.zeros_like(lc)
-            if last:
-                losses.update(loss_cls=lc, loss_bbox=lb, loss_occupancy=lo, loss_flow=torch.zeros_like(lc))
-            else:
-                losses['d%d.loss_cls' % lvl] = lc
-                losses['d%d.loss_bbox' % lvl] = lb
+            return list(zip(*self._losses_from_targets(all_cls, all_box, *targets))), None
+        boxes, labels = self._prepare_gts(gts, gt_labels, all_box.device)
+        last = len(all_cls) - 1
+        out = [self.loss_single(all_cls[lvl], all_box[lvl], occ if lvl == last else None, boxes, labels,
+                                gt_occupancy if lvl == last else None) for lvl in range(last + 1)]
+        return [o[:2] for o in out], out[-1][2]
+
+    @staticmethod
+    def _loss_dict(terms, **last):
+        """The reference's loss dict from the (loss_cls, loss_bbox) of every decoder layer: ``d{i}.loss_*`` of the earlier
+        layers, then the last layer's pair and its further terms ``last``, in that order (callers sum the values in it)."""
+        losses = {}
+        for lvl, (lc, lb) in enumerate(terms[:-1]):
+            losses['d%d.loss_cls' % lvl] = lc
+            losses['d%d.loss_bbox' % lvl] = lb
+        losses.update(loss_cls=terms[-1][0], loss_bbox=terms[-1][1], **last)
         return losses
 
     @staticmethod
     def _prepare_gts(gt_bboxes_list, gt_labels_list, device):
         """Boxes padded with zero velocity columns (head:1316-1317), labels as int64 tensors, on ``device``."""
-        padded = []
-        for g in gt_bboxes_list:
-            g = g.to(device)
-            if g.shape[-1] < 9:
-                g = torch.cat([g, g.new_zeros(g.shape[0], 9 - g.shape[-1])], dim=1)
-            padded.append(g)
-        labels = [torch.as_tensor(x, device=device).long() for x in gt_labels_list]
-        return padded, labels
+        boxes = [VoxelFormerOccupancyHead._boxes_as_tensor(g, device) for g in gt_bboxes_list]
+        return boxes, [torch.as_tensor(x, device=device).long() for x in gt_labels_list]
 
     def occupancy_targets(self, occ_gts, device=None):
         """The dataset's sparse occupancy annotation -> the dense target ``loss`` takes (head:1322-1326, :1404-1408):
@@ -862,14 +793,7 @@ class VoxelFormerOccupancyHead(BaseModule):
         reference's one-element list around it); every other voxel gets ``occupancy_classes`` = empty.
         -> int64 [bs, voxel_num]."""
         device = device if device is not None else self.code_weights.device
-        gt = torch.full((len(occ_gts), self.voxel_num), self.occupancy_classes, dtype=torch.long, device=device)
-        for b, pairs in enumerate(occ_gts):
-            if isinstance(pairs, (list, tuple)):                   # occ_gts[bs][queue_index]
-                pairs = pairs[0]
-            pairs = torch.as_tensor(pairs).long().to(device)
-            if pairs.numel():
-                gt[b, pairs[:, 0]] = pairs[:, 1]
-        return gt
+        return dense_labels(occ_gts, None, torch.long, self.occupancy_classes, self.voxel_num, device)
 
     def occupancy_targets_device(self, occ_gts, invalid=None, rows=None, device=None):
         """``occupancy_targets`` (and, with ``invalid``, ``occupancy_eval_labels``) without the dense int64 volume and the
@@ -914,19 +838,7 @@ class VoxelFormerOccupancyHead(BaseModule):
         voxels leave the visible mask.  -> uint8 [bs, voxel_num] in the reference's voxel order: ``occupancy_classes`` =
         empty, 255 = not evaluated (``occupancy_confusion`` ignores every label above ``occupancy_classes``)."""
         device = device if device is not None else self.code_weights.device
-        gt = torch.full((len(occ_gts), self.voxel_num), self.occupancy_classes, dtype=torch.uint8, device=device)
-        for b, pairs in enumerate(occ_gts):
-            if isinstance(pairs, (list, tuple)):                   # occ_gts[bs][queue_index]
-                pairs = pairs[0]
-            pairs = torch.as_tensor(pairs).long().to(device)
-            if pairs.numel():
-                gt[b, pairs[:, 0]] = pairs[:, 1].to(torch.uint8)
-            invalid = occ_invalid[b] if occ_invalid is not None else None
-            if invalid is not None:
-                invalid = torch.as_tensor(invalid).long().reshape(-1).to(device)
-                if invalid.numel():
-                    gt[b, invalid] = 255
-        return gt
+        return dense_labels(occ_gts, occ_invalid, torch.uint8, self.occupancy_classes, self.voxel_num, device)
 
     def occupancy_confusion(self, occupancy_preds, labels, thresholds=(0.25,), hist=None):
         """Confusion matrices of the occupancy prediction of ``get_occupancy_prediction`` at every threshold against
@@ -940,11 +852,7 @@ class VoxelFormerOccupancyHead(BaseModule):
         nc = self.occupancy_classes
         if isinstance(occupancy_preds, tuple):                         # (logits in GEMM row order, plan, bs)
             logits, plan, bs = occupancy_preds                         # [bs*X*Y, Z, classes], group-major rows
-            if isinstance(labels, OccupancyTargets):
-                gt = labels.ordered('rows', plan).view(-1, self.occ_zdim)
-            else:
-                gt = labels.reshape(bs, self.occ_zdim, plan.rows).permute(0, 2, 1)      # (Z, X, Y) order -> [bs, X*Y, Z]
-                gt = voxels_to_rows(gt, plan, bs)
+            gt = labels_in_rows(labels, plan, bs, self.occ_zdim)
             if hist is None:
                 hist = torch.zeros((bs, len(thresholds), nc + 1, nc + 1), dtype=torch.int64, device=logits.device)
             # the rows of sample b in group g are contiguous (row bs*offset_g + b*n_g + i): one call per group
@@ -953,8 +861,7 @@ class VoxelFormerOccupancyHead(BaseModule):
                 _confusion(logits[sl], gt[sl], bs, thresholds, hist)
             return hist
         bs = occupancy_preds.shape[0] if occupancy_preds.dim() == 3 else 1
-        if isinstance(labels, OccupancyTargets):
-            labels = labels.ordered('voxels').to(occupancy_preds.device)
+        labels = labels_in_voxels(labels).to(occupancy_preds.device)
         if hist is None:
             hist = torch.zeros((bs, len(thresholds), nc + 1, nc + 1), dtype=torch.int64, device=occupancy_preds.device)
         return _confusion(occupancy_preds, labels, bs, thresholds, hist)
@@ -975,9 +882,9 @@ class VoxelFormerOccupancyHead(BaseModule):
         """(image, vectors, eps) of the classifying MLP launches for the folded, centred chain: what ``OccMLPFunction``
         packs for ``_occ_mlp(first_folded=True)`` (W2 in W1's image section, b1 = 0)."""
         from ..hipops import occ_mlp_pack, occ_mlp_vectors
-        _, n1, _, l2, n2, _, l3 = list(self.occ_branches)
+        _, n1, _, _, n2, _, l3 = list(self.occ_branches)
+        w2c, b2c = self._centered_second_linear()
         with torch.autocast('cuda', enabled=False):
-            w2c, b2c = self._centered(l2.weight.float(), l2.bias.float())
             image = occ_mlp_pack(w2c, w2c, l3.weight)
             vec = occ_mlp_vectors(torch.zeros(128, device=w2c.device), n1.weight, n1.bias, b2c, n2.weight, n2.bias,
                                   l3.bias)
@@ -1000,11 +907,7 @@ class VoxelFormerOccupancyHead(BaseModule):
         from ..hipops import occ_mlp_confusion
         x, plan, bs = fused
         image, vec, eps = self._fused_eval_params()
-        if isinstance(labels, OccupancyTargets):
-            gt = labels.ordered('rows', plan).view(-1, self.occ_zdim)
-        else:
-            gt = labels.reshape(bs, self.occ_zdim, plan.rows).permute(0, 2, 1)          # (Z, X, Y) order -> [bs, X*Y, Z]
-            gt = voxels_to_rows(gt.to(torch.uint8), plan, bs)
+        gt = labels_in_rows(labels, plan, bs, self.occ_zdim, dtype=torch.uint8)
         if hist is None:
             hist = torch.zeros((bs, len(thresholds), nc + 1, nc + 1), dtype=torch.int64, device=x.device)
         z = self.occ_zdim
@@ -1026,9 +929,7 @@ class VoxelFormerOccupancyHead(BaseModule):
             cls = torch.full((flat.shape[0],), nc, dtype=torch.uint8, device=flat.device)
             cls[pairs[:, 0]] = pairs[:, 1].to(torch.uint8)
             return cls.view(lead)
-        p = flat.float().sigmoid()
-        p = torch.cat((p, torch.ones_like(p)[:, :1] * threshold), dim=-1)
-        return p.argmax(dim=-1).to(torch.uint8).view(lead)
+        return classify(flat, threshold).to(torch.uint8).view(lead)
 
     def occupancy_classes_from_volume(self, voxel_embed, threshold=0.25):
         """The dense class map of ``get_occupancy_prediction``: uint8 [bs, X*Y*Z] in the reference's (Z, X, Y) voxel
@@ -1068,32 +969,13 @@ class VoxelFormerOccupancyHead(BaseModule):
         """``only_det`` detectors (head:1619-1700): classification and box terms of every decoder layer, no
         occupancy term."""
         all_cls, all_box = preds_dicts['all_cls_scores'], preds_dicts['all_bbox_preds']
-        dev = all_box.device
-        fused = None
-        if isinstance(gt_bboxes_list, PaddedGts):
-            if not self._fused_solver():
-                raise ValueError("loss_only_detection: a PaddedGts needs train_cfg.assigner.solver = 'fused'")
-            fused = self._set_loss_fused(all_cls, all_box, gt_bboxes_list, self.loss_bbox)
-        else:
+        if not isinstance(gt_bboxes_list, PaddedGts):
             if not isinstance(gt_bboxes_list, (list, tuple)):
                 gt_bboxes_list, gt_labels_list = [gt_bboxes_list], [gt_labels_list]
-            boxes = [self._boxes_as_tensor(b, dev) for b in gt_bboxes_list]
-            labels = [torch.as_tensor(x, device=dev).long() for x in gt_labels_list]
-            if self._fused_solver():                         # every layer in one pass, no round trip per (layer, sample)
-                fused = self._set_loss_fused(all_cls, all_box, self.pad_gts(boxes, labels), self.loss_bbox)
-        nl = len(all_cls)
-        losses = {}
-        for lvl in range(nl):
-            if fused is not None:
-                lc, lb = fused[0][lvl], fused[1][lvl]
-            else:
-                lc, lb, _ = self.loss_single(all_cls[lvl], all_box[lvl], None, boxes, labels)
-            if lvl == nl - 1:
-                losses.update(loss_cls=lc, loss_bbox=lb)
-            else:
-                losses['d%d.loss_cls' % lvl] = lc
-                losses['d%d.loss_bbox' % lvl] = lb
-        return losses
+            gt_bboxes_list, gt_labels_list = self._prepare_gts(gt_bboxes_list, gt_labels_list, all_box.device)
+        terms, _ = self._detection_terms(all_cls, all_box, gt_bboxes_list, gt_labels_list, batched=False,
+                                         padded_error="loss_only_detection: a PaddedGts needs train_cfg.assigner.solver = 'fused'")
+        return self._loss_dict(terms)
 
     # ------------------------------------------------------------------ room-layout branch (add_layout=True)
     def _layout_targets_single(self, layout_pred, gt_layout):
@@ -1158,37 +1040,20 @@ class VoxelFormerOccupancyHead(BaseModule):
         dev = all_box.device
         if not isinstance(gt_bboxes_list, (list, tuple)):
             gt_bboxes_list, gt_labels_list, gt_layout_list = [gt_bboxes_list], [gt_labels_list], [gt_layout_list]
-        boxes = [self._boxes_as_tensor(b, dev) for b in gt_bboxes_list]
+        boxes, labels = self._prepare_gts(gt_bboxes_list, gt_labels_list, dev)
         layouts = [self._boxes_as_tensor(b, dev) for b in gt_layout_list]
-        labels = [torch.as_tensor(x, device=dev).long() for x in gt_labels_list]
-        nl = len(all_cls)
-        losses = {}
-        fused = None
-        if self._fused_solver():
-            # the detection terms of every layer in one pass; the last layer's layout term through the same kernels without
-            # class logits (cost, solve and loss of L = 1), its normaliser all-reduced on the device
-            fused = self._set_loss_fused(all_cls, all_box, self.pad_gts(boxes, labels), self.loss_bbox)
-            if all_box.is_cuda:
-                room = self.pad_gts(layouts, [g.new_zeros(g.shape[0], dtype=torch.long) for g in layouts])
-                fused_layout = self._set_loss_fused(None, all_layout[nl - 1:], room, self.loss_layout)[1][0]
-            else:
-                fused_layout = self._layout_term(all_layout[nl - 1], layouts, fused[0][nl - 1])
-        for lvl in range(nl):
-            last = lvl == nl - 1
-            if fused is not None:
-                lc, lb, ll = fused[0][lvl], fused[1][lvl], fused_layout if last else None
-                lo = self.occupancy_loss(occ, gt_occupancy) if (last and occ is not None) else torch.zeros_like(lc)
-            else:
-                lc, lb, ll, lo = self.loss_single_layout(all_cls[lvl], all_box[lvl], all_layout[lvl],
-                                                         occ if last else None, boxes, labels, layouts,
-                                                         gt_occupancy if last else None)
-            if last:
-                losses.update(loss_cls=lc, loss_bbox=lb, loss_occupancy=lo, loss_flow=torch.zeros_like(lc),
-                              loss_layout=ll)
-            else:
-                losses['d%d.loss_cls' % lvl] = lc
-                losses['d%d.loss_bbox' % lvl] = lb
-        return losses
+        last = len(all_cls) - 1
+        terms, lo = self._detection_terms(all_cls, all_box, boxes, labels, batched=False, occ=occ, gt_occupancy=gt_occupancy)
+        if self._fused_solver() and all_box.is_cuda:
+            # 'fused': the last layer's layout term through the same kernels without class logits (cost, solve and loss
+            # of L = 1), its normaliser all-reduced on the device
+            room = self.pad_gts(layouts, [g.new_zeros(g.shape[0], dtype=torch.long) for g in layouts])
+            ll = self._set_loss_fused(None, all_layout[last:], room, self.loss_layout)[1][0]
+        else:
+            ll = self._layout_term(all_layout[last], layouts, terms[last][0])
+        if lo is None:
+            lo = self._occupancy_term(occ, gt_occupancy, terms[last][0])
+        return self._loss_dict(terms, loss_occupancy=lo, loss_flow=torch.zeros_like(terms[last][0]), loss_layout=ll)
 
     def _to_box_type(self, boxes, img_meta):
         """head:1466-1471: bottom centre + the dataset's box class when the meta carries one."""
@@ -1245,18 +1110,14 @@ class VoxelFormerOccupancyHead(BaseModule):
     def _targets_begin(self, all_cls, all_box, gt_boxes, gt_labels):
         """First half of ``_batched_targets``: cost matrices on the device and their ASYNCHRONOUS copy into pinned host
         memory (an event marks its end).  Nothing here waits for the device."""
-        from .assigner import BBox3DL1Cost, FocalLossCost, linear_sum_assignment
-        a = self.assigner
-        if (a is None or linear_sum_assignment is None or not isinstance(a.cls_cost, FocalLossCost)
-                or not isinstance(a.reg_cost, BBox3DL1Cost)):
+        from .assigner import linear_sum_assignment
+        if linear_sum_assignment is None or not self._restated_costs():
             return None
-        nl, bs, nq, _ = all_cls.shape
         counts = [int(g.shape[0]) for g in gt_boxes]
         gmax = max(counts) if counts else 0
         if gmax == 0:
             return None
-        dev = all_box.device
-        gt_pad, lab_pad = self._pad_tables(gt_boxes, gt_labels, counts, gmax, all_box.dtype, dev)
+        gt_pad, lab_pad = self._pad_tables(gt_boxes, gt_labels, counts, gmax, all_box.dtype, all_box.device)
         with torch.no_grad():
             cost = self._assignment_costs(all_cls, all_box, gt_pad, lab_pad)
             event = None
@@ -1267,7 +1128,13 @@ class VoxelFormerOccupancyHead(BaseModule):
                 event.record()
             else:
                 host = cost
-        return dict(host=host, event=event, counts=counts, gt_pad=gt_pad, lab_pad=lab_pad, shape=(nl, bs, nq, gmax))
+        return dict(host=host, event=event, counts=counts, gt_pad=gt_pad, lab_pad=lab_pad)
+
+    def _restated_costs(self):
+        """The assigner's costs are ``FocalLossCost`` + ``BBox3DL1Cost``: the pair ``_assignment_costs`` and the kernels restate."""
+        from .assigner import BBox3DL1Cost, FocalLossCost
+        a = self.assigner
+        return a is not None and isinstance(a.cls_cost, FocalLossCost) and isinstance(a.reg_cost, BBox3DL1Cost)
 
     def _pad_tables(self, gt_boxes, gt_labels, counts, gmax, dtype, dev):
         """The per-sample gt lists as padded tables on ``dev``: boxes ``dtype`` [bs, gmax, 9] (velocity columns zero,
@@ -1324,22 +1191,12 @@ class VoxelFormerOccupancyHead(BaseModule):
         """Second half: wait for the copy (only), solve the assignments on the host, build the targets on the device."""
         if ctx is None:
             return None
-        from .assigner import linear_sum_assignment
-        import numpy as np
         if ctx['event'] is not None:
             ctx['event'].synchronize()
-        cost = ctx['host'].numpy()
-        nl, bs, nq, gmax = ctx['shape']
-        counts, gt_pad, lab_pad = ctx['counts'], ctx['gt_pad'], ctx['lab_pad']
-        dev = gt_pad.device
-        idx = np.full((nl, bs, nq), -1, dtype=np.int64)
-        for lvl in range(nl):
-            for i in range(bs):
-                if counts[i]:
-                    rows, cols = linear_sum_assignment(cost[lvl, i, :, :counts[i]])
-                    idx[lvl, i, rows] = cols
-        num_pos = (idx >= 0).reshape(nl, -1).sum(1).tolist()
-        idx_t = _to_device_async(torch.from_numpy(idx), dev)
+        gt_pad, lab_pad = ctx['gt_pad'], ctx['lab_pad']
+        idx = self._solve_on_host(ctx['host'].numpy(), ctx['counts'])
+        num_pos = (idx >= 0).reshape(idx.shape[0], -1).sum(1).tolist()
+        idx_t = _to_device_async(torch.from_numpy(idx), gt_pad.device)
         return self._targets_from_match(idx_t, gt_pad, lab_pad) + (num_pos,)
 
     # ---- the same targets without the round trip (train_cfg.assigner.solver = 'device')
@@ -1356,10 +1213,9 @@ class VoxelFormerOccupancyHead(BaseModule):
         ``_targets_from_match`` and ``_losses_from_targets`` state; nothing is copied to the host, so the call can be captured.
         ``all_cls`` None: the room-layout form (regression cost and L1 term alone, ``loss_box_module`` = ``loss_layout``).
         -> (loss_cls per layer, loss_bbox per layer).  CPU tensors: the torch formulas of ``solver='device'``."""
-        from .assigner import BBox3DL1Cost, FocalLossCost
         a = self.assigner
-        if (a is None or not isinstance(a.cls_cost, FocalLossCost) or not isinstance(a.reg_cost, BBox3DL1Cost)
-                or not isinstance(self.loss_cls, losses.FocalLoss) or not isinstance(loss_box_module, losses.L1Loss)):
+        if (not self._restated_costs() or not isinstance(self.loss_cls, losses.FocalLoss)
+                or not isinstance(loss_box_module, losses.L1Loss)):
             raise NotImplementedError("solver='fused' is built for FocalLossCost + BBox3DL1Cost assigners with FocalLoss + L1Loss")
         if not all_box.is_cuda:
             return self._losses_from_targets(all_cls, all_box, *self._targets_device(all_cls, all_box, gts))
@@ -1399,9 +1255,7 @@ class VoxelFormerOccupancyHead(BaseModule):
         can be captured.  -> (labels, bbox_targets, pos_mask, positives per layer as an int64 DEVICE tensor [L]).  A
         problem scipy would raise on leaves its queries unmatched and is reported by a later call (``AssignmentFlag``).
         CPU tensors: the same plumbing with scipy in place of the kernel."""
-        from .assigner import BBox3DL1Cost, FocalLossCost
-        a = self.assigner
-        if a is None or not isinstance(a.cls_cost, FocalLossCost) or not isinstance(a.reg_cost, BBox3DL1Cost):
+        if not self._restated_costs():
             raise NotImplementedError("solver='device' is built for FocalLossCost + BBox3DL1Cost assigners")
         nl, bs, nq, _ = all_cls.shape
         gt_pad, lab_pad, counts = gts.boxes.to(all_box.dtype), gts.labels, gts.counts
@@ -1417,7 +1271,8 @@ class VoxelFormerOccupancyHead(BaseModule):
                 idx_t = lsa_solve(cost, ncols, bad=flag.dev).long()
                 flag.mirror(None)
             else:
-                idx_t = self._solve_on_host(self._assignment_costs(all_cls, all_box, gt_pad, lab_pad), counts)
+                cost = self._assignment_costs(all_cls, all_box, gt_pad, lab_pad)
+                idx_t = torch.from_numpy(self._solve_on_host(cost.numpy(), counts.tolist()))
         labels, bbox_targets, pos_mask = self._targets_from_match(idx_t, gt_pad, lab_pad)
         # positives per layer, counted from the match like the host path: sum_b min(Nq, counts[b]) whenever every problem
         # was solved, and still the number of rows with a target when a flagged problem left its queries unmatched
@@ -1425,15 +1280,17 @@ class VoxelFormerOccupancyHead(BaseModule):
 
     @staticmethod
     def _solve_on_host(cost, counts):
-        """CPU stand-in of ``lsa_solve``: scipy on ``cost[l, b, :, :counts[b]]`` -> int64 [L, bs, Nq], -1 = unmatched."""
+        """The assignments on the host, as in the reference: scipy on ``cost[l, b, :, :counts[b]]`` of a numpy cost array
+        [L, bs, Nq, G] for a list of counts -> numpy int64 [L, bs, Nq], -1 = unmatched."""
         from .assigner import linear_sum_assignment
+        import numpy as np
         nl, bs, nq, _ = cost.shape
-        idx = torch.full((nl, bs, nq), -1, dtype=torch.long)
+        idx = np.full((nl, bs, nq), -1, dtype=np.int64)
         for lvl in range(nl):
-            for i, n in enumerate(counts.tolist()):
+            for i, n in enumerate(counts):
                 if n:
-                    rows, cols = linear_sum_assignment(cost[lvl, i, :, :n].numpy())
-                    idx[lvl, i, torch.from_numpy(rows)] = torch.from_numpy(cols)
+                    rows, cols = linear_sum_assignment(cost[lvl, i, :, :n])
+                    idx[lvl, i, rows] = cols
         return idx
 
     def _device_normalisers(self, num_pos, per_layer):
@@ -1510,9 +1367,7 @@ class VoxelFormerOccupancyHead(BaseModule):
             occ_results['occupancy_preds'] = occ_predict(logits, occ_threshold)
             occ_results['flow_preds'] = None
             return occ_results
-        p = logits.float().sigmoid()                     # fp32 like the kernel and the (fp32) reference
-        p = torch.cat((p, torch.ones_like(p)[:, :1] * occ_threshold), dim=-1)
-        occ_class = p.argmax(dim=-1)
+        occ_class = classify(logits, occ_threshold)      # fp32 like the kernel and the (fp32) reference
         occ_index, = torch.where(occ_class < self.occupancy_classes)
         occ_results['occupancy_preds'] = torch.stack([occ_index, occ_class[occ_index]], dim=-1)
         occ_results['flow_preds'] = None
