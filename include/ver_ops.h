@@ -854,6 +854,48 @@ int ver_occ_targets(const void* pairs, int pair_dtype, const int32_t* offsets, l
                     uint8_t* labels, int32_t* count, int32_t* bad, long voxel_num, int zdim, int classes, int bs,
                     void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Decoder 3-D deformable attention from the raw Linear outputs (additive to ABI 31; csrc/ver_dattn3d.hip): the reference's
+ * VoxelCustomMSDeformableAttention.forward between its three input Linears and output_proj
+ * (bevformer/modules/voxel_decoder.py:234-337) around voxel_multi_scale_deformable_attn_pytorch
+ * (voxel_temporal_self_attention.py:275-335) -- ver_msda3d_* with the softmax over the points and the sampling-location
+ * arithmetic inside the kernel, as ver_sca_* are to ver_msda_*.
+ *   value        f32 | bf16 [B, num_keys, heads, head_dim]     output of value_proj (value_dtype: 0 f32, 1 bf16)
+ *   shapes_dhw   i64 device [levels, 3] = (D, H, W);  level_start i64 device [levels]      as for ver_msda3d_forward
+ *   ref          f32 [B, Nq, levels, 3]                        (x, y, z) in [0, 1]
+ *   offsets      f32 | bf16 [B, Nq, heads, levels, points, 3]  raw Linear output (q_dtype)
+ *   logits       f32 | bf16 [B, Nq, heads, levels*points]      pre-softmax (q_dtype, the same as offsets)
+ *   out          f32 | bf16 [B, Nq, heads*head_dim]            written in full (out_dtype)
+ * All arithmetic is fp32, bf16 operands are widened first:
+ *   w   = softmax(logits) over the levels*points entries of a (query, head), the maximum subtracted
+ *   loc = ref[b,q,l] + offsets[b,q,h,l,p] / (W_l, H_l, D_l)          (the division, then the add)
+ *   out[b,q,h,:] = sum_{l,p} w * trilinear(value_l, loc)             (exactly ver_msda3d_forward's sampling: pixel =
+ *                  loc*size - 0.5, zeros outside, flat key (z*H + y)*W + x)
+ * ver_dattn3d_backward takes the same operands plus grad_out [B, Nq, heads*head_dim] in out_dtype and WRITES IN FULL, whatever
+ * the buffers held (the caller zeroes nothing):
+ *   grad_value   value_dtype, as value.  No float atomics: every cell is summed in fp32 by one wave in ascending (query,
+ *                level, point, corner) order and rounded once -- the same inputs give the same bits on every run
+ *   grad_offsets q_dtype, as offsets  = grad_loc / (W, H, D)
+ *   grad_logits  q_dtype, as logits   = w * (g_w - sum(w * g_w)), the softmax backward;  g_w and grad_loc are
+ *                ver_msda3d_backward's grad_attn_w and grad_loc
+ *   grad_ref     f32 [B, Nq, levels, 3] or NULL (not wanted): grad_loc summed over the heads (ascending), then the points,
+ *                in that fixed order
+ * One launch forward, two backward; no memset node, no allocation, no host read, no workspace: the calls can be captured.
+ * B == 0 or Nq == 0: VER_OK, nothing is launched and no pointer is looked at.  Another null pointer: VER_EINVAL.
+ * Supported (VER_EUNSUPPORTED beyond; ver_dattn3d_supported answers 1 / 0 for a shape without touching the device):
+ * levels*points <= 32, head_dim <= 128, heads <= 64, and B*Nq*heads and B*heads*ceil(num_keys/64) below 2^31.  The level
+ * geometry lives on the device and is not validated: sum(D*H*W) must equal num_keys (keys are clamped into the volume for
+ * reads and dropped for writes, so a wrong geometry gives wrong numbers, not a fault).
+ */
+int ver_dattn3d_supported(int B, int num_keys, int heads, int head_dim, int levels, int points, int Nq);
+int ver_dattn3d_forward(const void* value, int value_dtype, const int64_t* shapes_dhw, const int64_t* level_start,
+                        const float* ref, const void* offsets, const void* logits, int q_dtype, void* out, int out_dtype,
+                        int B, int num_keys, int heads, int head_dim, int levels, int points, int Nq, void* stream);
+int ver_dattn3d_backward(const void* value, int value_dtype, const int64_t* shapes_dhw, const int64_t* level_start,
+                         const float* ref, const void* offsets, const void* logits, int q_dtype, const void* grad_out,
+                         int out_dtype, void* grad_value, void* grad_offsets, void* grad_logits, float* grad_ref,
+                         int B, int num_keys, int heads, int head_dim, int levels, int points, int Nq, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

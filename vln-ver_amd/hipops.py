@@ -1239,6 +1239,80 @@ def voxel_msda(value, spatial_shapes, level_start_index, sampling_locations, att
                                            attention_weights)
 
 
+def _lowp(t, name):
+    """fp32 and bf16 operands go to the kernels as they are; anything else is widened to fp32."""
+    t = _gpu(t, name)
+    return t if t.dtype in (torch.float32, torch.bfloat16) else t.float()
+
+
+def voxel_deform_attn_supported(bs, num_keys, heads, head_dim, levels, points, num_query):
+    """Whether ver_dattn3d_* take the shape (the range is stated in include/ver_ops.h); no device call."""
+    return bool(lib().ver_dattn3d_supported(bs, num_keys, heads, head_dim, levels, points, num_query))
+
+
+class VoxelDeformAttnFunction(Function):
+    """The detection decoder's 3-D deformable attention from the raw Linear outputs (ver_dattn3d_forward / _backward):
+    softmax over the points, loc = ref + offsets / (W, H, D) and the trilinear sampling in one launch, the backward in two,
+    with every gradient written in full (no zero fills) and a reproducible grad_value."""
+
+    @staticmethod
+    def forward(ctx, value, spatial_shapes, level_start_index, reference_points, offsets, logits, out_dtype=None):
+        value = _lowp(value, 'value')
+        offsets = _lowp(offsets, 'offsets')
+        logits = _lowp(logits, 'logits')
+        if logits.dtype != offsets.dtype:
+            logits = logits.to(offsets.dtype)
+        ref = _gpu(reference_points, 'reference_points').float().contiguous()
+        shapes = _gpu(spatial_shapes, 'spatial_shapes').to(torch.int64).contiguous()
+        lsi = _gpu(level_start_index, 'level_start_index').to(torch.int64).contiguous()
+        bs, nk, heads, hd = value.shape
+        _, nq, _, nl, npt, _ = offsets.shape
+        assert logits.shape == (bs, nq, heads, nl * npt) and ref.shape == (bs, nq, nl, 3)
+        vdt = 1 if value.dtype == torch.bfloat16 else 0
+        qdt = 1 if offsets.dtype == torch.bfloat16 else 0
+        out_dtype = out_dtype or value.dtype
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError('out_dtype must be torch.float32 or torch.bfloat16, got %s' % out_dtype)
+        odt = 1 if out_dtype == torch.bfloat16 else 0
+        out = torch.empty(bs, nq, heads * hd, dtype=out_dtype, device=value.device)
+        _launch('ver_dattn3d_forward', lambda: lib().ver_dattn3d_forward(
+            _p(value), vdt, _p(shapes), _p(lsi), _p(ref), _p(offsets), _p(logits), qdt, _p(out), odt, bs, nk, heads, hd, nl,
+            npt, nq, _stream()))
+        ctx.save_for_backward(value, shapes, lsi, ref, offsets, logits)
+        ctx.ref_like = (reference_points.shape, reference_points.dtype)
+        ctx.out_dtype = out_dtype
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        value, shapes, lsi, ref, offsets, logits = ctx.saved_tensors
+        bs, nk, heads, hd = value.shape
+        _, nq, _, nl, npt, _ = offsets.shape
+        vdt = 1 if value.dtype == torch.bfloat16 else 0
+        qdt = 1 if offsets.dtype == torch.bfloat16 else 0
+        odt = 1 if ctx.out_dtype == torch.bfloat16 else 0
+        go = _gpu(grad_output, 'grad_output').to(ctx.out_dtype).contiguous()
+        # (an empty query set launches nothing: only then is there something to clear)
+        gv = torch.empty_like(value) if bs * nq else torch.zeros_like(value)
+        goff, glog = torch.empty_like(offsets), torch.empty_like(logits)
+        gref = torch.empty_like(ref) if ctx.needs_input_grad[3] else None
+        _launch('ver_dattn3d_backward', lambda: lib().ver_dattn3d_backward(
+            _p(value), vdt, _p(shapes), _p(lsi), _p(ref), _p(offsets), _p(logits), qdt, _p(go), odt, _p(gv), _p(goff),
+            _p(glog), _p(gref), bs, nk, heads, hd, nl, npt, nq, _stream()))
+        shape, dtype = ctx.ref_like
+        return gv, None, None, None if gref is None else gref.view(shape).to(dtype), goff, glog, None
+
+
+def voxel_deform_attn(value, spatial_shapes, level_start_index, reference_points, offsets, logits, out_dtype=None):
+    """value f32|bf16 [bs,Nk,heads,hd] (value_proj's output), reference_points [bs,Nq,L,3] in [0,1], offsets f32|bf16
+    [bs,Nq,heads,L,P,3] and logits [bs,Nq,heads,L*P] (the raw outputs of sampling_offsets / attention_weights) ->
+    [bs,Nq,heads*hd] in ``out_dtype`` (fp32 | bf16; None: value's).  bf16 operands are passed through; a shape outside the
+    library's range raises with its message."""
+    return VoxelDeformAttnFunction.apply(value, spatial_shapes, level_start_index, reference_points, offsets, logits,
+                                         out_dtype)
+
+
 # ------------------------------------------------------------------------------------------
 def occ_predict(logits, threshold=0.25):
     """Sparse occupancy prediction (ver_occ_predict; head:1505-1540): logits fp32|bf16 [N, C] ->

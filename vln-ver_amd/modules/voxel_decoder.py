@@ -52,12 +52,19 @@ def voxel_multi_scale_deformable_attn(value, value_spatial_shapes, sampling_loca
 
 @ATTENTION.register_module(force=True)
 class VoxelCustomMSDeformableAttention(BaseModule):
-    """voxel_decoder.py:135-337 (sequence-first, with output_proj + dropout + identity)."""
+    """voxel_decoder.py:135-337 (sequence-first, with output_proj + dropout + identity).
 
+    ``fused``: True hands the outputs of ``sampling_offsets``, ``attention_weights`` and ``value_proj`` straight to
+    ``hipops.voxel_deform_attn`` (softmax, sampling locations and sampling in one launch; reproducible gradients), False keeps
+    the torch softmax / location arithmetic in front of ``voxel_msda``, None = the class attribute ``fused_sampling``.
+    Parameters, state dict and config are the same either way."""
+
+    fused_sampling = False
 
     def __init__(self, embed_dims=256, num_heads=8, num_levels=4, num_points=4, im2col_step=64,
-                 dropout=0.1, batch_first=False, norm_cfg=None, init_cfg=None):
+                 dropout=0.1, batch_first=False, norm_cfg=None, init_cfg=None, fused=None):
         super().__init__(init_cfg)
+        self.fused = fused
         if embed_dims % num_heads != 0:
             raise ValueError(f'embed_dims must be divisible by num_heads, '
                              f'but got {embed_dims} and {num_heads}')
@@ -117,12 +124,17 @@ class VoxelCustomMSDeformableAttention(BaseModule):
         value = value.view(bs, num_value, self.num_heads, -1)
         offsets = self.sampling_offsets(query).view(bs, num_query, self.num_heads, self.num_levels,
                                                     self.num_points, 3)
-        weights = self.attention_weights(query).view(bs, num_query, self.num_heads,
-                                                     self.num_levels * self.num_points).softmax(-1)
-        weights = weights.view(bs, num_query, self.num_heads, self.num_levels, self.num_points)
         if reference_points.shape[-1] != 3:
             raise ValueError(f'Last dim of reference_points must be 3, '
                              f'but get {reference_points.shape[-1]} instead.')
+        if self.fused_sampling if self.fused is None else self.fused:
+            output = self._fused_sampling(value, offsets, self.attention_weights(query), reference_points, spatial_shapes,
+                                          level_start_index)
+            # (under autocast output_proj takes the kernel's bf16 rows as they are)
+            return self._project(output if torch.is_autocast_enabled() else output.to(query.dtype), identity, defer_residual)
+        weights = self.attention_weights(query).view(bs, num_query, self.num_heads,
+                                                     self.num_levels * self.num_points).softmax(-1)
+        weights = weights.view(bs, num_query, self.num_heads, self.num_levels, self.num_points)
         normalizer = const_tensor([[float(s[2]), float(s[1]), float(s[0])] for s in shapes], offsets.device, offsets.dtype)
         loc = reference_points[:, :, None, :, None, :] + offsets / normalizer[None, None, None, :, None, :]
         if not value.is_cuda:
@@ -133,7 +145,24 @@ class VoxelCustomMSDeformableAttention(BaseModule):
             sizes = spatial_shapes.prod(1)
             level_start_index = torch.cat([sizes.new_zeros(1), sizes.cumsum(0)[:-1]])
         output = voxel_msda(value, spatial_shapes, level_start_index, loc, weights)
-        output = self.output_proj(output.to(query.dtype))
+        return self._project(output.to(query.dtype), identity, defer_residual)
+
+    def _fused_sampling(self, value, offsets, logits, reference_points, spatial_shapes, level_start_index):
+        """``hipops.voxel_deform_attn`` on the raw Linear outputs (bf16 under autocast: passed through as they are)."""
+        if not value.is_cuda:
+            raise RuntimeError('VoxelCustomMSDeformableAttention runs only on the GPU (HIP kernels); '
+                               'there is no CPU fallback in this package')
+        from ..hipops import voxel_deform_attn
+        bs, num_query = offsets.shape[:2]
+        if level_start_index is None:
+            sizes = spatial_shapes.prod(1)
+            level_start_index = torch.cat([sizes.new_zeros(1), sizes.cumsum(0)[:-1]])
+        ref = reference_points.expand(bs, num_query, self.num_levels, 3)
+        logits = logits.view(bs, num_query, self.num_heads, self.num_levels * self.num_points)
+        return voxel_deform_attn(value, spatial_shapes, level_start_index, ref, offsets, logits)
+
+    def _project(self, output, identity, defer_residual):
+        output = self.output_proj(output)
         if not self.batch_first:
             output = output.permute(1, 0, 2)
         if defer_residual:                  # the LayerNorm that follows adds the residual (bricks.residual_layer_norm)
