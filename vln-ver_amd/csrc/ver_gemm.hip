@@ -19,6 +19,11 @@
 //     ver_gemm_nn_splitk); tiles are dealt to the XCDs in contiguous
 //     ranges, the N tiles of one row block next to each other, so that the 32 tiles in flight on an XCD share their A
 //     rows and W columns in its L2.
+// MFMA shape: v_mfma_f32_32x32x16_bf16, measured against v_mfma_f32_16x16x32_bf16 at the same 128 x 64 wave tile (one k-step
+// of 8 x 4 tiles per phase, A fragment = chunk l >> 4 of row l & 15, W fragments from both slabs, swizzles re-derived: all
+// tests passed).  On N(0,1) operands the explicit kernel gained 3.0 % (11.49 -> 11.16 ms on the layer-3 product), the implicit
+// forms -- 98 of this body's 110 ms per 192-viewpoint step -- lost 17-31 %, and the two are compared bit for bit, so they
+// cannot take different shapes: not kept (profiles/gemm_mfma_shape_32_vs_16.jsonl).  ver_wgrad.hip runs 16x16x32.
 #include "ver_common.h"
 
 namespace {

@@ -6,37 +6,67 @@
 //
 // Both operands are row-major with the CONTRACTION index on the slow axis, which is the one layout class the library
 // answers with depth-32 macro-tiles (0.35-0.43 of the bf16 peak).  Here:
-//   * rows are streamed in slabs of 16 (one k-step of v_mfma_f32_32x32x16_bf16) straight into LDS by LDS-DMA
-//     (buffer_load_dwordx4 ... lds): a wave instruction moves 8 rows x 128 B, i.e. whole 128-byte lines of the source;
+//   * rows are streamed in slabs of 16 straight into LDS by LDS-DMA (buffer_load_dwordx4 ... lds): a wave instruction
+//     moves 8 rows x 128 B, i.e. whole 128-byte lines of the source;
+//   * the MFMA is v_mfma_f32_16x16x32_bf16 (kShape; the v_mfma_f32_32x32x16_bf16 form, one slab per k-step, is the
+//     body's other value: 2.8 % slower on N(0,1) operands): a k-step spans the slab PAIR 2p, 2p + 1 --
+//     k-groups 0-1 (lanes 0-31) are rows 0-7 / 8-15 of the first slab, k-groups 2-3 of the second.  An odd slab count is
+//     rounded up: rows past M read as zeros (buffer range; implicit A: an offset outside every range);
 //   * the MFMA fragments (8 consecutive k of ONE column per lane) come out of that row-major image through
-//     ds_read_b64_tr_b16, two per fragment; the 16-byte chunks of a 128-byte line are XOR-ed by bit 1 of the row on the
-//     SOURCE address (the LDS-DMA destination is lane-linear), which makes every transposing read conflict free;
-//   * a workgroup of 8 waves (2 x 4, wave tile 128 x 64 = 4 x 2 MFMA tiles, 128 accumulator registers) owns a
+//     ds_read_b64_tr_b16, two per fragment; the 16-byte chunks of a 128-byte line are XOR-ed on the SOURCE address (the
+//     LDS-DMA destination is lane-linear) by bit 1 of the row and, in rows 8-15 of a slab, by the 32-byte pair -- the two
+//     16-lane groups of a half read the same columns of rows 0-7 and 8-15 -- which makes every transposing read conflict free;
+//   * a workgroup of 8 waves (2 x 4, wave tile 128 x 64 = 8 x 4 MFMA tiles, 128 accumulator registers) owns a
 //     256 x 256 output tile of one row chunk; the two wave groups (wr = 0 / 1, one wave of each per SIMD) run
-//     half a phase apart: while one issues its 12 fragment reads + 2 LDS-DMA pieces of the slab PF phases ahead, the
-//     other issues its 8 MFMAs (ring of 8 slabs = 128 KB, counted vmcnt, raw s_barrier);
+//     half a phase apart: while one issues its 24 fragment reads + 4 LDS-DMA pieces of the slab pair two phases ahead,
+//     the other issues its 32 MFMAs (ring of 8 slabs = 128 KB, counted vmcnt, raw s_barrier);
 //   * split over row chunks: block b runs on XCD b % 8 and XCD x works on chunks x, x + 8, ...: the rows of a chunk are
 //     fetched into ONE L2, where the ~32 tiles of the XCD that are in flight share them; fp32 partial tiles go to a
 //     workspace and k_wgrad_reduce adds them up in fp32 (no bf16 rounding of partial sums).
-#include <cstdlib>
 #include "ver_common.h"
 
 namespace {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int kTile = 256;                  // output tile edge
-constexpr int kSlabRows = 16;               // rows per slab = k of one MFMA
+constexpr int kSlabRows = 16;               // rows per slab: the k of one 32x32x16 MFMA, half the k of a 16x16x32
 constexpr int kSlabBytes = 2 * kSlabRows * kTile * 2;   // A part + G part
 constexpr int kRing = 8;
 constexpr int kLdsBytes = kRing * kSlabBytes;           // 128 KiB
 
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// MFMA shape of the body (compile time, as in ver_gemm.hip): 32 = v_mfma_f32_32x32x16_bf16, one slab of 16 rows per k-step,
+// 4 x 2 tiles per wave; 16 = v_mfma_f32_16x16x32_bf16, a k-step spans the slab PAIR 2p, 2p + 1 (k-groups 0-1 from the first,
+// 2-3 from the second), 8 x 4 tiles per wave -- phases of two slabs (KP == 2) only.
+constexpr int kShape = 16;
+template <int SH>
+struct Shape {
+    typedef f32x16 acc_t;
+    static constexpr int NI = 4, NJ = 2, NR = 16, TW = 32;
+    // accumulator register r of a lane: row reg_row(r) + lane_row(lane) of the tile, column lane & (TW - 1)
+    static __device__ __forceinline__ int reg_row(int r) { return (r & 3) + 8 * (r >> 2); }
+    static __device__ __forceinline__ int lane_row(int lane) { return 4 * (lane >> 5); }
+    // source-side swizzle of a piece (8 rows x 128 B): position p of row `row` of row group `rowhalf` holds chunk p ^ swz
+    static __device__ __forceinline__ int swz(int row, int rowhalf) { return ((row >> 1) & 1) << 2; }
+};
+template <>
+struct Shape<16> {
+    typedef f32x4 acc_t;
+    static constexpr int NI = 8, NJ = 4, NR = 4, TW = 16;
+    static __device__ __forceinline__ int reg_row(int r) { return r; }
+    static __device__ __forceinline__ int lane_row(int lane) { return 4 * (lane >> 4); }
+    // the two 16-lane groups of a half read the SAME 16 columns of rows 0-7 and 8-15 of a slab (k-groups g, g + 1), 4 KiB
+    // apart: rows 8-15 swap their 32-byte column pairs and the half covers all 64 banks
+    static __device__ __forceinline__ int swz(int row, int rowhalf) { return (((row >> 1) & 1) << 2) ^ (rowhalf << 1); }
+};
 
 // ds_read_b64_tr_b16 as inline asm: behind the builtin the compiler waits for vmcnt(0) in front of every LDS read
 // that follows an LDS-DMA (it cannot tell the ring slots apart), which would serialise the whole pipeline.  The
@@ -93,6 +123,7 @@ struct WTapLane {       // implicit A: the lane's running row of the DMA stream,
     int tend;                   // LDS byte address one past the wave's table (wrap -> next viewpoint)
     int rows_left;              // rows of the operand from the next row to request on (<= 0: past the chunk / M)
     int vo;                     // voffset of the next piece to request (made in the MFMA shadow of the phase before)
+    int taddr1, pend1, vo1;     // two slabs per phase: the same three for the SECOND slab of the next phase
 };
 
 // The wave's offset table (one per 64-column block of the tile, 4 per workgroup, behind the ring in LDS): entry pos = byte
@@ -128,8 +159,27 @@ __device__ __forceinline__ void wtap_step(const WgradArgs& t, WTapLane& tl, int 
     if (tl.taddr >= tl.tend) tl.taddr -= 4 * t.P, tl.pend = tl.bstep;
 }
 
+// two slabs per phase: both table entries fetched in this phase become the next phase's two voffsets, then the addresses of
+// the two entries after them are made ready
+__device__ __forceinline__ void wtap_step2(const WgradArgs& t, WTapLane& tl, int tfetched0, int tfetched1) {
+    tl.boff += tl.pend;
+    tl.rows_left -= kSlabRows;
+    tl.vo = tl.rows_left > 0 ? (int)((unsigned)tfetched0 + (unsigned)tl.boff) : kOutsideW;
+    tl.boff += tl.pend1;
+    tl.rows_left -= kSlabRows;
+    tl.vo1 = tl.rows_left > 0 ? (int)((unsigned)tfetched1 + (unsigned)tl.boff) : kOutsideW;
+    tl.taddr = tl.taddr1 + 4 * kSlabRows;
+    tl.pend = 0;
+    if (tl.taddr >= tl.tend) tl.taddr -= 4 * t.P, tl.pend = tl.bstep;
+    tl.taddr1 = tl.taddr + 4 * kSlabRows;
+    tl.pend1 = 0;
+    if (tl.taddr1 >= tl.tend) tl.taddr1 -= 4 * t.P, tl.pend1 = tl.bstep;
+}
+
 struct WgradLane {          // per-lane constants of the main loop
-    int offA0, offA1, offB0, offB1;     // LDS byte addresses of the fragment reads in ring slot 0
+    // LDS byte addresses of the fragment reads in ring slot 0 -- 32x32x16: [0], [1] = column tiles 0 / 1 of a 64-column block;
+    // 16x16x32: the four 16-column tiles of a block, in the lane's slab of the pair and row half
+    int offA[4], offB[4];
     int voA, voG;                       // per-lane source offsets of the two LDS-DMA pieces this wave moves
     int stepA, stepG;                   // bytes per slab of the sources
     int dmaoff;                         // offset of this wave's piece inside the A / G part of a slab
@@ -141,7 +191,7 @@ __device__ __forceinline__ void read_slab(const WgradLane& c, i32x2 (&al)[4], i3
     // (the offset field of a DS instruction has 16 bits: slots 4-7 go through base registers 64 KiB up)
     constexpr int SB = (SLOT & 3) * kSlabBytes;
     constexpr int UP = SLOT >= 4 ? 65536 : 0;
-    const int a0 = c.offA0 + UP, a1 = c.offA1 + UP, b0 = c.offB0 + UP, b1 = c.offB1 + UP;
+    const int a0 = c.offA[0] + UP, a1 = c.offA[1] + UP, b0 = c.offB[0] + UP, b1 = c.offB[1] + UP;
     al[0] = tr_read<SB>(a0);
     ah[0] = tr_read<SB + 512>(a0);
     bl[0] = tr_read<SB>(b0);
@@ -156,7 +206,71 @@ __device__ __forceinline__ void read_slab(const WgradLane& c, i32x2 (&al)[4], i3
     ah[3] = tr_read<SB + 1536>(a1);
 }
 
-// One phase = KP slabs (ring slots PS*KP ..): fragments -> registers, LDS-DMA of the slabs PF ahead, 8 KP MFMAs.
+// 16x16x32: one phase = the slab pair in ring slots 2 PS, 2 PS + 1 = ONE k-step.  The 16-lane group g of a wave reads rows
+// 8 (g & 1) .. + 7 of slab g >> 1 (both in its base addresses): 8 A tiles + 4 G tiles of 16 columns, two transposing reads
+// each -- the 24 reads of two 32x32x16 slabs; then the LDS-DMA of the pair PF slabs ahead and 32 MFMAs.
+template <int PS, int KP, int PF, int IMPL>
+__device__ __forceinline__ void phase(char* lds, f32x4 (&acc)[8][4], const WgradLane& c, __amdgpu_buffer_rsrc_t ra,
+                                      __amdgpu_buffer_rsrc_t rg, unsigned& soA, unsigned& soG, const WgradArgs& t, WTapLane& tl) {
+    static_assert(KP == 2, "16x16x32: a k-step is a slab pair");
+    constexpr int SB = ((2 * PS) & 3) * kSlabBytes;
+    constexpr int UP = 2 * PS >= 4 ? 65536 : 0;
+    i32x2 al[8], ah[8], bl[4], bh[4];
+    int tn0 = 0, tn1 = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int a = c.offA[q] + UP, b = c.offB[q] + UP;
+        al[q] = tr_read<SB>(a);
+        ah[q] = tr_read<SB + 512>(a);
+        bl[q] = tr_read<SB>(b);
+        bh[q] = tr_read<SB + 512>(b);
+        al[4 + q] = tr_read<SB + 1024>(a);
+        ah[4 + q] = tr_read<SB + 1536>(a);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int ds = (2 * PS + u + PF) % kRing;
+        if constexpr (IMPL < 0) {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(lds + ds * kSlabBytes + c.dmaoff), 16, c.voA, (int)soA, 0, 0);
+        } else {
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(lds + ds * kSlabBytes + c.dmaoff), 16, u ? tl.vo1 : tl.vo, 0, 0, 0);
+            if (u) tn1 = lds_read_b32(tl.taddr1);          // the entries of the two rows after (consumed in the MFMA shadow)
+            else tn0 = lds_read_b32(tl.taddr);
+        }
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rg, (lds_void*)(lds + ds * kSlabBytes + kSlabBytes / 2 + c.dmaoff), 16, c.voG, (int)soG, 0, 0);
+        soA += (unsigned)c.stepA;
+        soG += (unsigned)c.stepG;
+    }
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (PF - KP)) : "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(al[0]), "+v"(ah[0]), "+v"(al[1]), "+v"(ah[1]), "+v"(al[2]), "+v"(ah[2]), "+v"(al[3]), "+v"(ah[3]), "+v"(al[4]),
+                   "+v"(ah[4]), "+v"(al[5]), "+v"(ah[5]), "+v"(al[6]), "+v"(ah[6]), "+v"(al[7]), "+v"(ah[7]), "+v"(bl[0]), "+v"(bh[0]),
+                   "+v"(bl[1]), "+v"(bh[1]), "+v"(bl[2]), "+v"(bh[2]), "+v"(bl[3]), "+v"(bh[3]), "+v"(tn0), "+v"(tn1)
+                 :
+                 : "memory");
+    bf16x8 a[8], b[4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = frag(al[i], ah[i]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b[j] = frag(bl[j], bh[j]);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int it = 0; it < 8; ++it)
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt)
+            acc[it][jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[it], b[jt], acc[it][jt], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (IMPL >= 0) {
+        wtap_step2(t, tl, tn0, tn1);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __builtin_amdgcn_s_barrier();
+}
+
+// 32x32x16: one phase = KP slabs (ring slots PS*KP ..): fragments -> registers, LDS-DMA of the slabs PF ahead, 8 KP MFMAs.
 template <int PS, int KP, int PF, int IMPL>
 __device__ __forceinline__ void phase(char* lds, f32x16 (&acc)[4][2], const WgradLane& c, __amdgpu_buffer_rsrc_t ra,
                                       __amdgpu_buffer_rsrc_t rg, unsigned& soA, unsigned& soG, const WgradArgs& t, WTapLane& tl) {
@@ -222,8 +336,8 @@ __device__ __forceinline__ void phase(char* lds, f32x16 (&acc)[4][2], const Wgra
     __builtin_amdgcn_s_barrier();
 }
 
-template <int PS, int KP, int PF, int IMPL>
-__device__ __forceinline__ void phases_from(int left, char* lds, f32x16 (&acc)[4][2], const WgradLane& c,
+template <int PS, int KP, int PF, int IMPL, typename ACC>
+__device__ __forceinline__ void phases_from(int left, char* lds, ACC& acc, const WgradLane& c,
                                             __amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rg, unsigned& soA, unsigned& soG,
                                             const WgradArgs& t, WTapLane& tl) {
     if constexpr (PS < kRing / KP) {
@@ -234,9 +348,11 @@ __device__ __forceinline__ void phases_from(int left, char* lds, f32x16 (&acc)[4
     }
 }
 
-template <int KP, int PF, int IMPL>
+template <int SH, int KP, int PF, int IMPL>
 __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
+    typedef Shape<SH> sh;
     static_assert(PF >= KP && PF + (KP == 1 ? 2 : 4) <= kRing, "prefetch distance against the ring (WAR on the slot)");
+    static_assert(SH == 32 || KP == 2, "16x16x32: a k-step is a slab pair");
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -268,7 +384,7 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
     const long gbytes = ((p.M - row0 - 1) * p.ldg + p.N - (long)nt * kTile) * 2;
     const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)gb, 0, (int)max(0L, min(gbytes, 0xFFFFFFFFL)), 0x00020000);
     WgradLane c;
-    const int prow = lane >> 3, pch = (lane & 7) ^ (((prow >> 1) & 1) << 2);
+    const int prow = lane >> 3, pch = (lane & 7) ^ sh::swz(prow, wave >> 2);
     // implicit A: the segment of this wave's 64 columns (boundaries are multiples of 64) -> its source (lattice or pattern
     // table) and tap; the lane's first row
     WTapLane tl = {};
@@ -318,24 +434,37 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
 
     // transposing fragment reads: 16-lane group q = (k half, column half), lane c of it addresses row c >> 2,
     // columns 4 (c & 3) .. + 3 and receives column c of the group's 4 x 16 block
-    {
+    if constexpr (SH == 32) {
         const int q = lane >> 4, cl = lane & 15;
-        const int lowch = (2 * (q & 1) + ((cl & 3) >> 1)) ^ (((cl >> 3) & 1) << 2);
+        const int lowch = (2 * (q & 1) + ((cl & 3) >> 1)) ^ sh::swz(cl >> 2, q >> 1);
         const int lbase = (int)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
         const int rowoff = lbase + ((q >> 1) * 32 + (cl >> 2)) * 128 + lowch * 16 + (cl & 1) * 8;
-        c.offA0 = rowoff + 2 * wr * 1024;
-        c.offA1 = c.offA0 ^ 64;
-        c.offB0 = rowoff + wc * 1024 + kSlabBytes / 2;
-        c.offB1 = c.offB0 ^ 64;
+        c.offA[0] = rowoff + 2 * wr * 1024;
+        c.offA[1] = c.offA[0] ^ 64;
+        c.offB[0] = rowoff + wc * 1024 + kSlabBytes / 2;
+        c.offB[1] = c.offB[0] ^ 64;
+        c.offA[2] = c.offA[3] = c.offB[2] = c.offB[3] = 0;
+    } else {
+        // 16x16x32: 16-lane group g = k-group: rows 8 (g & 1) .. + 7 (piece row group g & 1, 4 KiB up) of slab g >> 1 of the
+        // pair; lane c of it addresses row c >> 2 (and + 4), chunk 2 t + ((c & 3) >> 1) of column tile t, half c & 1
+        const int g = lane >> 4, cl = lane & 15;
+        const int lbase = (int)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int ch = (2 * q + ((cl & 3) >> 1)) ^ sh::swz(cl >> 2, g & 1);
+            const int rowoff = lbase + (g >> 1) * kSlabBytes + (g & 1) * 4096 + (cl >> 2) * 128 + ch * 16 + (cl & 1) * 8;
+            c.offA[q] = rowoff + 2 * wr * 1024;
+            c.offB[q] = rowoff + wc * 1024 + kSlabBytes / 2;
+        }
     }
 
-    f32x16 acc[4][2];
+    typename sh::acc_t acc[sh::NI][sh::NJ];
 #pragma unroll
-    for (int it = 0; it < 4; ++it)
+    for (int it = 0; it < sh::NI; ++it)
 #pragma unroll
-        for (int jt = 0; jt < 2; ++jt)
+        for (int jt = 0; jt < sh::NJ; ++jt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[it][jt][r] = 0.0f;
+            for (int r = 0; r < sh::NR; ++r) acc[it][jt][r] = 0.0f;
 
     // prologue: slabs 0 .. PF-1 in flight, the first phase's slabs landed
 #pragma unroll
@@ -352,6 +481,18 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
         soA += (unsigned)c.stepA;
         soG += (unsigned)c.stepG;
     }
+    if constexpr (IMPL >= 0 && KP == 2) {
+        // two slabs per phase: tl.vo is slab PF's piece; fetch one more entry for slab PF + 1, then the addresses of the two after
+        const int vo0 = tl.vo;
+        int tn = lds_read_b32(tl.taddr);
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tn)::"memory");
+        wtap_step(p, tl, tn);
+        tl.vo1 = tl.vo;
+        tl.vo = vo0;
+        tl.taddr1 = tl.taddr + 4 * kSlabRows;
+        tl.pend1 = 0;
+        if (tl.taddr1 >= tl.tend) tl.taddr1 -= 4 * p.P, tl.pend1 = tl.bstep;
+    }
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (PF - KP)) : "memory");
     __builtin_amdgcn_s_barrier();
     if (wr == 1) __builtin_amdgcn_s_barrier();          // the second wave group runs half a phase behind
@@ -362,19 +503,20 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
     if (wr == 0) __builtin_amdgcn_s_barrier();          // barrier counts of the two groups match again
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the run-ahead pieces nobody reads
 
-    // partial tile -> workspace: register r of tile (it, jt) is row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31
-    const int i0 = mt * kTile + 128 * wr + 4 * (lane >> 5), j0 = nt * kTile + 64 * wc + (lane & 31);
+    // partial tile -> workspace: register r of tile (it, jt) is row reg_row(r) + lane_row(lane), column lane & (TW - 1) --
+    // 32x32x16: (r & 3) + 8 (r >> 2) + 4 (lane >> 5), lane & 31;  16x16x32: r + 4 (lane >> 4), lane & 15
+    const int i0 = mt * kTile + 128 * wr + sh::lane_row(lane), j0 = nt * kTile + 64 * wc + (lane & (sh::TW - 1));
     if (p.S == 1 && p.out) {
         // one row chunk: there is nothing to add up -- the same fp32 sums, rounded once, straight into the result (a
         // one-viewpoint step has 450 / 1 800 rows: the workspace round trip was 10 of its 12 bytes per element)
 #pragma unroll
-        for (int it = 0; it < 4; ++it)
+        for (int it = 0; it < sh::NI; ++it)
 #pragma unroll
-            for (int jt = 0; jt < 2; ++jt) {
-                const int j = j0 + 32 * jt;
+            for (int jt = 0; jt < sh::NJ; ++jt) {
+                const int j = j0 + sh::TW * jt;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int i = i0 + 32 * it + (r & 3) + 8 * (r >> 2);
+                for (int r = 0; r < sh::NR; ++r) {
+                    const int i = i0 + sh::TW * it + sh::reg_row(r);
                     if (i < p.Ka && j < p.N) {
                         if (p.out_bf16)
                             reinterpret_cast<__bf16*>(p.out)[(long)i * p.ldo + j] = (__bf16)acc[it][jt][r];
@@ -387,27 +529,32 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
     }
     float* out = p.ws + (long)chunk * p.Ka * p.N;
 #pragma unroll
-    for (int it = 0; it < 4; ++it)
+    for (int it = 0; it < sh::NI; ++it)
 #pragma unroll
-        for (int jt = 0; jt < 2; ++jt) {
-            const int j = j0 + 32 * jt;
+        for (int jt = 0; jt < sh::NJ; ++jt) {
+            const int j = j0 + sh::TW * jt;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = i0 + 32 * it + (r & 3) + 8 * (r >> 2);
+            for (int r = 0; r < sh::NR; ++r) {
+                const int i = i0 + sh::TW * it + sh::reg_row(r);
                 if (i < p.Ka && j < p.N) out[(long)i * p.N + j] = acc[it][jt][r];
             }
         }
 }
 
-template <int KP, int PF>
+// slabs per phase and prefetch distance (in slabs) of the product's shape: 16x16x32 a slab pair, requested two phases ahead
+// like ver_gemm.hip's; 32x32x16 one slab, three ahead (the best of the distances 3-6 and of the pair forms measured in round 5)
+constexpr int kKP = kShape == 16 ? 2 : 1;
+constexpr int kPF = kShape == 16 ? 4 : 3;
+
+template <int SH>
 __global__ __launch_bounds__(512) void k_wgrad_tn(WgradArgs p) {
-    wgrad_body<KP, PF, -1>(p);
+    wgrad_body<SH, kKP, kPF, -1>(p);
 }
 
 // the same kernel with the implicit tap matrix of a lattice in layout L as A (ver_wgrad_tn_segments)
-template <int L, int PF>
+template <int L, int SH>
 __global__ __launch_bounds__(512) void k_wgrad_tn_seg(WgradArgs p) {
-    wgrad_body<1, PF, L>(p);
+    wgrad_body<SH, kKP, kPF, L>(p);
 }
 
 // out[i][j] (bf16 or fp32, row pitch ldo) = sum over the S partial products, fp32; 4 elements per thread
@@ -482,29 +629,17 @@ int pick_splits(long M, int Ka, int N, long ld = 0) {
     return best;
 }
 
-template <int KP, int PF>
 void launch_tn(const WgradArgs& p, int blocks, hipStream_t st, hipError_t& e) {
-    auto kern = k_wgrad_tn<KP, PF>;
+    auto kern = k_wgrad_tn<kShape>;
     e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
     if (e == hipSuccess) hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), kLdsBytes, st, p);
-}
-template <int L, int PF>
-void launch_tn_segments_pf(const WgradArgs& p, int blocks, hipStream_t st, hipError_t& e) {
-    const int ldsb = kLdsBytes + 4 * p.P * 4;            // the ring + four offset tables of P ints
-    e = hipFuncSetAttribute((const void*)k_wgrad_tn_seg<L, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);
-    if (e == hipSuccess) hipLaunchKernelGGL((k_wgrad_tn_seg<L, PF>), dim3((unsigned)blocks), dim3(512), ldsb, st, p);
 }
 
 template <int L>
 void launch_tn_segments(const WgradArgs& p, int blocks, hipStream_t st, hipError_t& e) {
-    static const int pf = [] {                             // (prefetch distance in slabs; VER_WGRAD_SEG_PF: experiments)
-        const char* v = getenv("VER_WGRAD_SEG_PF");
-        return v ? atoi(v) : 3;
-    }();
-    if (pf == 4) launch_tn_segments_pf<L, 4>(p, blocks, st, e);
-    else if (pf == 5) launch_tn_segments_pf<L, 5>(p, blocks, st, e);
-    else if (pf == 6) launch_tn_segments_pf<L, 6>(p, blocks, st, e);
-    else launch_tn_segments_pf<L, 3>(p, blocks, st, e);
+    const int ldsb = kLdsBytes + 4 * p.P * 4;            // the ring + four offset tables of P ints
+    e = hipFuncSetAttribute((const void*)k_wgrad_tn_seg<L, kShape>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);
+    if (e == hipSuccess) hipLaunchKernelGGL((k_wgrad_tn_seg<L, kShape>), dim3((unsigned)blocks), dim3(512), ldsb, st, p);
 }
 }  // namespace
 
@@ -530,6 +665,7 @@ extern "C" int ver_wgrad_tn(const void* a, long lda, const void* g, long ldg, lo
     VER_REQUIRE(M >= 0 && Ka > 0 && N > 0, VER_EINVAL, "ver_wgrad_tn: bad sizes M=%ld Ka=%d N=%d", M, Ka, N);
     VER_REQUIRE(out && workspace && ((a && g) || M == 0), VER_EINVAL, "ver_wgrad_tn: null pointer argument");
     VER_REQUIRE(out_dtype == VER_F32 || out_dtype == VER_BF16, VER_EINVAL, "ver_wgrad_tn: out_dtype %d", out_dtype);
+    VER_REQUIRE(flags == 0, VER_EINVAL, "ver_wgrad_tn: unknown flags 0x%x", flags);
     VER_REQUIRE(lda >= Ka && ldg >= N && ldo >= N, VER_EINVAL, "ver_wgrad_tn: row pitch smaller than the row");
     VER_REQUIRE(lda % 8 == 0 && ldg % 8 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)g & 15) == 0, VER_EUNSUPPORTED,
                 "ver_wgrad_tn: operands must be 16-byte aligned with row pitches that are multiples of 8 elements");
@@ -561,14 +697,7 @@ extern "C" int ver_wgrad_tn(const void* a, long lda, const void* g, long ldg, lo
     p.out_bf16 = out_dtype == VER_BF16;
     hipError_t e = hipSuccess;
     if (M > 0) {
-        switch (flags & 15) {
-            case 4: launch_tn<1, 4>(p, p.T * S, st, e); break;
-            case 5: launch_tn<1, 5>(p, p.T * S, st, e); break;
-            case 6: launch_tn<1, 6>(p, p.T * S, st, e); break;
-            case 8 + 2: launch_tn<2, 2>(p, p.T * S, st, e); break;
-            case 8 + 4: launch_tn<2, 4>(p, p.T * S, st, e); break;
-            default: launch_tn<1, 3>(p, p.T * S, st, e); break;
-        }
+        launch_tn(p, p.T * S, st, e);
         if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_wgrad_tn: LDS attribute: %s", hipGetErrorString(e));
     } else if (int zrc = ver_zero_async(workspace, (size_t)S * Ka * N * sizeof(float), st)) {   // (kernel zero fill: ver_zero_async)
         return zrc;
