@@ -9,26 +9,33 @@
 // phase apart, LDS-DMA ring, counted vmcnt, raw barriers); what differs is the operand with the contraction index on its
 // FAST axis:
 //   * A tile rows are streamed as [256 rows][32 k] images (64 B per row; a wave instruction moves 16 rows x 64 B), their
-//     16-byte chunks XOR-ed by bits 2-3 of the row on the SOURCE address, and the MFMA fragment of a lane (8 consecutive k
-//     of one row) is ONE ds_read_b128, conflict free by that swizzle;
+//     16-byte chunks XOR-ed on the SOURCE address by a function of the row's quarter of its 16-row tile (Shape::swz_a), and
+//     the MFMA fragment of a lane (8 consecutive k of one row) is ONE ds_read_b128, conflict free by that swizzle;
 //   * W is streamed in 16-row slabs and read through ds_read_b64_tr_b16 exactly as both operands of k_wgrad_tn;
-//   * a phase is 32 of K (two MFMA k-steps: 8 + 8 fragment reads, 4 LDS-DMA pieces, 16 MFMAs per wave), the ring holds
-//     four phases (128 KB), pieces are requested two phases ahead;
+//   * a phase is 32 of K = ONE k-step of v_mfma_f32_16x16x32_bf16 (8 + 8 fragment reads, 4 LDS-DMA pieces, 32 MFMAs per
+//     wave on 8 x 4 tiles; k-groups 0-1 of a lane group come from W slab 0, 2-3 from slab 1), the ring holds four phases
+//     (128 KB), pieces are requested two phases ahead;
+//   * implicit operand: the stream's place on the K axis (segment, channel offset, segment length, the current buffer
+//     resource) is wave-uniform and lives in SGPRs; the K axis is described by one packed 32-bit descriptor per segment in
+//     the kernel-argument block, and the descriptor of segment t + 1 is requested by a scalar load when segment t begins, so
+//     a segment switch is scalar work + the two lanes' offset arithmetic: the main loop holds no vector-memory instruction
+//     but the LDS-DMA pieces and no vmcnt wait but the counted vmcnt(4), and no instantiation has a private segment;
 //   * no split over K for the tall products (K = 6 304 .. 38 400 here: 197+ phases per tile; skinny ones -- the 450- and
 //     1 800-row operands of a one-viewpoint step, 12-42 tiles -- are cut into K slices with fp32 partial tiles, see
 //     ver_gemm_nn_splitk); tiles are dealt to the XCDs in contiguous
 //     ranges, the N tiles of one row block next to each other, so that the 32 tiles in flight on an XCD share their A
 //     rows and W columns in its L2.
-// MFMA shape: v_mfma_f32_32x32x16_bf16, measured against v_mfma_f32_16x16x32_bf16 at the same 128 x 64 wave tile (one k-step
-// of 8 x 4 tiles per phase, A fragment = chunk l >> 4 of row l & 15, W fragments from both slabs, swizzles re-derived: all
-// tests passed).  On N(0,1) operands the explicit kernel gained 3.0 % (11.49 -> 11.16 ms on the layer-3 product), the implicit
-// forms -- 98 of this body's 110 ms per 192-viewpoint step -- lost 17-31 %, and the two are compared bit for bit, so they
-// cannot take different shapes: not kept (profiles/gemm_mfma_shape_32_vs_16.jsonl).  ver_wgrad.hip runs 16x16x32.
+// MFMA shape: v_mfma_f32_16x16x32_bf16 (kShape; the v_mfma_f32_32x32x16_bf16 form, two k-steps of 4 x 2 tiles per phase,
+// is the body's other value).  With the tap stream as it was first written -- the lane's two offsets in scratch memory, read
+// back in front of the A requests of every phase, and the tap tables read by dependent vector loads at every switch -- the
+// implicit forms lost 17-31 % on 16x16x32; with the stream in registers both shapes gain, 16x16x32 more (DESIGN.md 3.3,
+// profiles/gemm_tap_stream_ab.jsonl).  Implicit and explicit entry points are compared bit for bit and share the shape.
 #include "ver_common.h"
 
 namespace {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
@@ -37,6 +44,42 @@ constexpr int kTile = 256;
 constexpr int kStageBytes = 32768;          // A image [256][32] (16 KB) + two W slabs [16][256] (2 x 8 KB)
 constexpr int kStages = 4;
 constexpr int kLdsBytes = kStages * kStageBytes;
+
+// MFMA shape of the body (compile time, as in ver_wgrad.hip): 32 = v_mfma_f32_32x32x16_bf16, two k-steps of 4 x 2 tiles per
+// phase; 16 = v_mfma_f32_16x16x32_bf16, ONE k-step of 8 x 4 tiles per phase (k-groups 0-1 from W slab 0, 2-3 from slab 1).
+constexpr int kShape = 16;
+template <int SH>
+struct Shape {
+    typedef f32x16 acc_t;
+    static constexpr int NI = 4, NJ = 2, NR = 16, TW = 32;
+    // accumulator register r of a lane: row reg_row(r) + lane_row(lane) of the tile, column lane & (TW - 1)
+    static __device__ __forceinline__ int reg_row(int r) { return (r & 3) + 8 * (r >> 2); }
+    static __device__ __forceinline__ int lane_row(int lane) { return 4 * (lane >> 5); }
+    // A image (64-byte rows): position p of row `row` holds source chunk p ^ swz_a(row).  Lane (i = l & 31, k half l >> 5)
+    // reads chunk (2 step + (l >> 5)) of row i: every 16-lane group of a ds_read_b128 covers the 16 slots of a bank row
+    static __device__ __forceinline__ int swz_a(int row) { return (row >> 2) & 3; }
+    // W slab piece (8 rows x 128 B) of row group `rowhalf`: position p of row `row` holds chunk p ^ swz_w (ver_wgrad.hip)
+    static __device__ __forceinline__ int swz_w(int row, int rowhalf) { return ((row >> 1) & 1) << 2; }
+};
+template <>
+struct Shape<16> {
+    typedef f32x4 acc_t;
+    static constexpr int NI = 8, NJ = 4, NR = 4, TW = 16;
+    static __device__ __forceinline__ int reg_row(int r) { return r; }
+    static __device__ __forceinline__ int lane_row(int lane) { return 4 * (lane >> 4); }
+    // lane (i = l & 15, k-group c = l >> 4) reads chunk c of row i.  The 16-lane groups of a ds_read_b128 are lanes {0-3,
+    // 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32: per row-in-four, a group holds (c, row quarter h = i >> 2) =
+    // (0, 0), (0, 3), (1, 1), (1, 2) -- or (1, 0), (1, 3), (0, 1), (0, 2) -- whose positions c ^ f(h) must differ:
+    // f = (0, 3, 2, 1) = -h gives {0, 1, 2, 3}
+    static __device__ __forceinline__ int swz_a(int row) { return (0 - (row >> 2)) & 3; }
+    // the two 16-lane groups of a half read the SAME 16 columns of rows 0-7 and 8-15 of a slab, 4 KiB apart: rows 8-15 swap
+    // their 32-byte column pairs and the half covers all 64 banks (ver_wgrad.hip)
+    static __device__ __forceinline__ int swz_w(int row, int rowhalf) { return (((row >> 1) & 1) << 2) ^ (rowhalf << 1); }
+};
+typedef Shape<kShape> sh;
+static_assert(Shape<32>::NI * Shape<32>::TW == 128 && Shape<32>::NJ * Shape<32>::TW == 64 && Shape<32>::NI * Shape<32>::NJ * Shape<32>::NR == 128 &&
+                  Shape<16>::NI * Shape<16>::TW == 128 && Shape<16>::NJ * Shape<16>::TW == 64 && Shape<16>::NI * Shape<16>::NJ * Shape<16>::NR == 128,
+              "a wave tile is 128 x 64 in 128 accumulator registers");
 
 // LDS reads as inline asm: behind the builtins the compiler waits for vmcnt(0) in front of every LDS read that follows an
 // LDS-DMA (ver_wgrad.hip).  Results are valid behind the s_waitcnt lgkmcnt(0) of phase().
@@ -65,15 +108,16 @@ struct TapArgs {
     long lattice_bytes;
     int B, H, W, C, ntaps, P;           // H, W: the combined lattice = the rows' grid; P = 2 H W rows per viewpoint
     const float* rowpos;                // [P][N] fp32 or null: added to row r's result by its position r % P
-    // constant-pattern segments (kind[t] = 1): CW columns that depend on the row's POSITION r % P only -- block dz[t] of
+    // constant-pattern segments (descriptor bit 31): CW columns that depend on the row's POSITION r % P only -- a block of
     // cst [P][ncst][CW] bf16 (dense_heads/upsample.py: the 0/1 patterns of the bias-valued odd positions + the 1 column)
     const __bf16* cst;
     long cst_bytes;
     int CW, ncst;
-    signed char kind[64], dz[64], dy[64], dx[64];
+    // one packed descriptor per segment of the K axis (filled by the launcher, read by scalar loads one segment ahead):
+    // bits 0-7 dx, 8-15 dy (signed bytes), 16-21 dz in {0, 2} or the pattern block, 22-27 the source plane, bit 31 = pattern
+    unsigned desc[64];
     // several source lattices of one shape `plane_elems` elements apart (the four class planes of a layer's output gradient,
-    // ver_gemm_nn_segments' d(input) form): tap t reads plane pl[t]; lattice_bytes is the size of ONE plane
-    signed char pl[64];
+    // ver_gemm_nn_segments' d(input) form): a tap reads the plane its descriptor names; lattice_bytes is the size of ONE plane
     long plane_elems;
 };
 
@@ -90,8 +134,9 @@ struct GemmArgs {
 };
 
 struct GemmLane {
-    int offA0, offA1;       // A fragment reads of k-step 0 / 1 of a phase (stage 0, row tile 0)
-    int offB0, offB1;       // W fragment reads (stage 0, slab 0, column tile 0 / 1)
+    int offA0, offA1;       // A fragment reads (stage 0, row tile 0): 32x32x16 k-step 0 / 1 of a phase; 16x16x32: offA0 only
+    int offB[4];            // W fragment reads (stage 0): 32x32x16 slab 0, column tile 0 / 1; 16x16x32: the four 16-column
+                            // tiles, in the lane's slab and row half
     int voA, voW;           // per-lane source offsets of this wave's LDS-DMA pieces
     int stepW;              // bytes per 16-row slab of W
     int stepA16;            // bytes per 16 rows of A (second LDS-DMA piece of a wave)
@@ -116,75 +161,142 @@ __device__ __forceinline__ int cell_off(const TapArgs& t, int b, int zl, int y, 
     return v * t.C * 2;
 }
 
-struct TapLane {                // implicit operand: this lane's two rows and the running segment / channel of its DMA stream
+struct TapLane {                // implicit operand, per lane (VGPRs): the lane's two rows and their current source offsets
     int b1, zl1, y1, x1, b2, zl2, y2, x2;
     int pos1, pos2;             // r % P of the two rows (constant-pattern segments)
     int vo1, vo2;               // byte offsets of the current segment's vectors (+ this lane's 16-byte chunk)
     int chunk;                  // pch * 16
-    int tap, ch;                // wave-uniform: segment and byte offset inside it of the NEXT piece to request
-    int seglen, is_cst;         // wave-uniform: bytes of the current segment; it is read from the pattern table
+};
+struct TapWave {                // implicit operand, per wave (SGPRs): the DMA stream's place on the K axis
+    int tap, ch;                // segment and byte offset inside it of the NEXT piece to request
+    int seglen;                 // bytes of the current segment
+    unsigned next;              // descriptor of segment tap + 1, loaded when segment tap began
+    const __attribute__((address_space(4))) unsigned* tab;     // TapArgs::desc in the kernel-argument block
 };
 
+// descriptor `idx` by a scalar load the compiler does not see: the result is valid behind the next s_waitcnt lgkmcnt(0), which
+// the caller owes before the first use (desc_ready() / the phase's own wait, which takes ts.next as an operand so that no use
+// is scheduled in front of it).  The register must not be copied in between either: when the compiler changes, look at the
+// switch path of the main loop in the ISA -- the one-phase-segment cases of tests/test_gemm_tap_stream_gpu.py
+// switch in every phase and compare exactly.
+__device__ __forceinline__ unsigned desc_load(const TapWave& ts, int idx) {
+    unsigned v;
+    asm volatile("s_load_dword %0, %1, %2" : "=s"(v) : "s"(ts.tab), "s"(idx * 4) : "memory");
+    return v;
+}
+__device__ __forceinline__ void desc_ready(unsigned& d) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(d) : : "memory"); }
+
+// segment ts.tap begins: its descriptor d -> the lane's two source offsets, the segment's length and the buffer resource its
+// pieces go through (the pattern table, or the tap's plane of the lattice).  Everything but o1 / o2 is scalar work.
 template <int L>
-__device__ __forceinline__ void tap_offsets(const TapArgs& t, TapLane& tl, __amdgpu_buffer_rsrc_t& ra) {
-    if (t.plane_elems && tl.tap < t.ntaps && !t.kind[tl.tap])
-        ra = __builtin_amdgcn_make_buffer_rsrc((void*)(t.lattice + (long)t.pl[tl.tap] * t.plane_elems), 0,
+__device__ __forceinline__ void tap_begin(const TapArgs& t, TapLane& tl, TapWave& ts, unsigned d, __amdgpu_buffer_rsrc_t& ra,
+                                          __amdgpu_buffer_rsrc_t rcst) {
+    const bool live = ts.tap < t.ntaps;                     // (pieces requested past the last phase: nobody reads them)
+    const bool is_cst = live && (d >> 31) != 0;
+    const int dx = (int)(d << 24) >> 24, dy = (int)(d << 16) >> 24, dz = (int)(d >> 16) & 63, pl = (int)(d >> 22) & 63;
+    int o1 = kOutside, o2 = kOutside, seglen = 2 * t.C;
+    if (is_cst) {
+        seglen = 2 * t.CW;
+        if (tl.b1 >= 0) o1 = (tl.pos1 * t.ncst + dz) * t.CW * 2 + tl.chunk;
+        if (tl.b2 >= 0) o2 = (tl.pos2 * t.ncst + dz) * t.CW * 2 + tl.chunk;
+        ra = rcst;
+    } else if (live) {
+        const int c1 = cell_off<L>(t, tl.b1, tl.zl1, tl.y1 + dy, tl.x1 + dx, dz);
+        const int c2 = cell_off<L>(t, tl.b2, tl.zl2, tl.y2 + dy, tl.x2 + dx, dz);
+        if (c1 != kOutside) o1 = c1 + tl.chunk;
+        if (c2 != kOutside) o2 = c2 + tl.chunk;
+        ra = __builtin_amdgcn_make_buffer_rsrc((void*)(t.lattice + (long)pl * t.plane_elems), 0,
                                                (int)max(0L, min(t.lattice_bytes, 0x7FFFFFFFL)), 0x00020000);
-    tl.is_cst = 0;
-    tl.seglen = 2 * t.C;
-    if (tl.tap < t.ntaps) {
-        const int dz = t.dz[tl.tap], dy = t.dy[tl.tap], dx = t.dx[tl.tap];
-        if (t.kind[tl.tap]) {
-            tl.is_cst = 1;
-            tl.seglen = 2 * t.CW;
-            tl.vo1 = tl.b1 < 0 ? kOutside : (tl.pos1 * t.ncst + dz) * t.CW * 2 + tl.chunk;
-            tl.vo2 = tl.b2 < 0 ? kOutside : (tl.pos2 * t.ncst + dz) * t.CW * 2 + tl.chunk;
-        } else {
-            const int o1 = cell_off<L>(t, tl.b1, tl.zl1, tl.y1 + dy, tl.x1 + dx, dz);
-            const int o2 = cell_off<L>(t, tl.b2, tl.zl2, tl.y2 + dy, tl.x2 + dx, dz);
-            tl.vo1 = o1 == kOutside ? kOutside : o1 + tl.chunk;
-            tl.vo2 = o2 == kOutside ? kOutside : o2 + tl.chunk;
-        }
-    } else {
-        tl.vo1 = tl.vo2 = kOutside;                          // (pieces requested past the last phase: nobody reads them)
     }
+    ts.seglen = seglen;
+    tl.vo1 = o1;
+    tl.vo2 = o2;
 }
 
-// this wave's two A pieces of one phase: explicit operand (IMPL < 0) or straight from the lattice
-template <int IMPL>
+// this wave's two A pieces of one phase: explicit operand (IMPL < 0) or straight from the lattice.  PRO: the prologue's two
+// requests follow each other without the phase's lgkmcnt(0) in between, so a descriptor loaded by the first is waited for here.
+template <int IMPL, bool PRO>
 __device__ __forceinline__ void request_a(char* dst, const GemmLane& c, __amdgpu_buffer_rsrc_t& ra, __amdgpu_buffer_rsrc_t rcst,
-                                          int& soA, const TapArgs& t, TapLane& tl) {
+                                          int& soA, const TapArgs& t, TapLane& tl, TapWave& ts) {
     if constexpr (IMPL < 0) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)dst, 16, c.voA, soA, 0, 0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(dst + 1024), 16, c.voA, soA + c.stepA16, 0, 0);
         soA += 64;
     } else {
-        const int ch = __builtin_amdgcn_readfirstlane(tl.ch);
-        if (__builtin_amdgcn_readfirstlane(tl.is_cst)) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rcst, (lds_void*)dst, 16, tl.vo1, ch, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rcst, (lds_void*)(dst + 1024), 16, tl.vo2, ch, 0, 0);
-        } else {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)dst, 16, tl.vo1, ch, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(dst + 1024), 16, tl.vo2, ch, 0, 0);
-        }
-        tl.ch = ch + 64;
-        if (tl.ch == __builtin_amdgcn_readfirstlane(tl.seglen)) {    // next segment: the lane's two source vectors move
-            tl.ch = 0;
-            tl.tap = __builtin_amdgcn_readfirstlane(tl.tap) + 1;
-            tap_offsets<IMPL>(t, tl, ra);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)dst, 16, tl.vo1, ts.ch, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(dst + 1024), 16, tl.vo2, ts.ch, 0, 0);
+        ts.ch += 64;
+        if (ts.ch == ts.seglen) {                           // next segment: the lane's two source vectors move
+            ts.ch = 0;
+            ts.tap += 1;
+            const unsigned d = ts.next;
+            ts.next = desc_load(ts, min(ts.tap + 1, t.ntaps - 1));
+            if constexpr (PRO) desc_ready(ts.next);
+            tap_begin<IMPL>(t, tl, ts, d, ra, rcst);
         }
     }
 }
 
-
+// 16x16x32: one phase = ONE k-step of 32: 8 row reads (the lane's chunk of its row in the eight 16-row tiles), 8 transposing
+// reads (4 column tiles, k halves lo / hi of the lane's slab and row group), the LDS-DMA of the phase two ahead, 32 MFMAs.
 template <int ST, int IMPL>
-__device__ __forceinline__ void phase(char* lds, f32x16 (&acc)[4][2], const GemmLane& c, __amdgpu_buffer_rsrc_t& ra,
-                                      __amdgpu_buffer_rsrc_t rw, int& soA, int& soW, const TapArgs& t, TapLane& tl,
+__device__ __forceinline__ void phase(char* lds, f32x4 (&acc)[8][4], const GemmLane& c, __amdgpu_buffer_rsrc_t& ra,
+                                      __amdgpu_buffer_rsrc_t rw, int& soA, int& soW, const TapArgs& t, TapLane& tl, TapWave& ts,
                                       __amdgpu_buffer_rsrc_t rcst) {
     // (the offset field of a DS instruction has 16 bits: stages 2-3 go through base registers 64 KiB up)
     constexpr int SB = (ST & 1) * kStageBytes;
     constexpr int UP = ST >= 2 ? 65536 : 0;
-    const int a0 = c.offA0 + UP, a1 = c.offA1 + UP, b0 = c.offB0 + UP, b1 = c.offB1 + UP;
+    const int a0 = c.offA0 + UP;
+    i32x4 av[8];
+    i32x2 bl[4], bh[4];
+    av[0] = row_read<SB>(a0);
+    av[1] = row_read<SB + 1024>(a0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int b = c.offB[q] + UP;
+        bl[q] = tr_read<SB + 16384>(b);
+        bh[q] = tr_read<SB + 16384 + 512>(b);
+        if (q == 0) av[2] = row_read<SB + 2048>(a0), av[3] = row_read<SB + 3072>(a0);
+        if (q == 1) av[4] = row_read<SB + 4096>(a0), av[5] = row_read<SB + 5120>(a0);
+        if (q == 2) av[6] = row_read<SB + 6144>(a0), av[7] = row_read<SB + 7168>(a0);
+    }
+    constexpr int DS = ((ST + 2) % kStages) * kStageBytes;
+    request_a<IMPL, false>(lds + DS + c.dmaA, c, ra, rcst, soA, t, tl, ts);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_void*)(lds + DS + 16384 + c.dmaW), 16, c.voW, soW, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_void*)(lds + DS + 24576 + c.dmaW), 16, c.voW, soW + c.stepW, 0, 0);
+    soW += 2 * c.stepW;
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // this wave's pieces of the NEXT phase have landed
+    __builtin_amdgcn_s_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(av[0]), "+v"(av[1]), "+v"(av[2]), "+v"(av[3]), "+v"(av[4]), "+v"(av[5]), "+v"(av[6]), "+v"(av[7]), "+v"(bl[0]),
+                   "+v"(bh[0]), "+v"(bl[1]), "+v"(bh[1]), "+v"(bl[2]), "+v"(bh[2]), "+v"(bl[3]), "+v"(bh[3])
+                 :
+                 : "memory");
+    if constexpr (IMPL >= 0) asm volatile("" : "+s"(ts.next));      // (a descriptor requested in this phase: valid from here)
+    bf16x8 a[8], b[4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = __builtin_bit_cast(bf16x8, av[i]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b[j] = frag(bl[j], bh[j]);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int it = 0; it < 8; ++it)
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) acc[it][jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[it], b[jt], acc[it][jt], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+}
+
+// 32x32x16: one phase = two k-steps of 16 (8 + 8 fragment reads, 16 MFMAs on 4 x 2 tiles)
+template <int ST, int IMPL>
+__device__ __forceinline__ void phase(char* lds, f32x16 (&acc)[4][2], const GemmLane& c, __amdgpu_buffer_rsrc_t& ra,
+                                      __amdgpu_buffer_rsrc_t rw, int& soA, int& soW, const TapArgs& t, TapLane& tl, TapWave& ts,
+                                      __amdgpu_buffer_rsrc_t rcst) {
+    constexpr int SB = (ST & 1) * kStageBytes;
+    constexpr int UP = ST >= 2 ? 65536 : 0;
+    const int a0 = c.offA0 + UP, a1 = c.offA1 + UP, b0 = c.offB[0] + UP, b1 = c.offB[1] + UP;
     i32x4 av[2][4];
     i32x2 bl[2][2], bh[2][2];
     // k-step 0: A chunks (l >> 5), W slab 0; k-step 1: A chunks 2 + (l >> 5), W slab 1
@@ -206,7 +318,7 @@ __device__ __forceinline__ void phase(char* lds, f32x16 (&acc)[4][2], const Gemm
     av[1][3] = row_read<SB + 6144>(a1);
     // LDS-DMA of the phase two ahead: this wave's 2 x 16 rows of the A image and its piece of each W slab
     constexpr int DS = ((ST + 2) % kStages) * kStageBytes;
-    request_a<IMPL>(lds + DS + c.dmaA, c, ra, rcst, soA, t, tl);
+    request_a<IMPL, false>(lds + DS + c.dmaA, c, ra, rcst, soA, t, tl, ts);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_void*)(lds + DS + 16384 + c.dmaW), 16, c.voW, soW, 0, 0);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_void*)(lds + DS + 24576 + c.dmaW), 16, c.voW, soW + c.stepW, 0, 0);
     soW += 2 * c.stepW;
@@ -218,6 +330,7 @@ __device__ __forceinline__ void phase(char* lds, f32x16 (&acc)[4][2], const Gemm
                    "+v"(bl[1][1]), "+v"(bh[1][1])
                  :
                  : "memory");
+    if constexpr (IMPL >= 0) asm volatile("" : "+s"(ts.next));      // (a descriptor requested in this phase: valid from here)
     bf16x8 a[2][4], b[2][2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -269,31 +382,46 @@ __global__ __launch_bounds__(512) void k_gemm_nn(GemmArgs p) {
     GemmLane c;
     {
         // A image piece: 16 rows x 64 B per instruction; lane -> (row l >> 2, position l & 3), position p holds source
-        // chunk p ^ ((row >> 2) & 3).  This wave moves rows 32 w .. 32 w + 31 (two instructions, + 16 rows = + 1 KiB).
+        // chunk p ^ Shape::swz_a(row).  This wave moves rows 32 w .. 32 w + 31 (two instructions, + 16 rows = + 1 KiB).
         const int prow = 32 * wave + (lane >> 2);
-        const int pch = (lane & 3) ^ ((prow >> 2) & 3);
+        const int pch = (lane & 3) ^ sh::swz_a(prow & 15);
         c.voA = (int)(prow * p.lda * 2) + pch * 16;
         c.dmaA = wave * 2048;
         c.stepA16 = (int)(16 * p.lda * 2);          // (second instruction: rows + 16; same swizzle term)
-        // W slab piece: 8 rows x 128 B, chunks XOR-ed by bit 1 of the row (ver_wgrad.hip)
-        const int wrow = lane >> 3, wch = (lane & 7) ^ (((wrow >> 1) & 1) << 2);
+        // W slab piece: 8 rows x 128 B, chunks XOR-ed by Shape::swz_w (ver_wgrad.hip)
+        const int wrow = lane >> 3, wch = (lane & 7) ^ sh::swz_w(wrow, wave >> 2);
         c.voW = (int)(((8 * (wave >> 2) + wrow) * p.ldw + 64 * (wave & 3)) * 2) + wch * 16;
         c.stepW = (int)(16 * p.ldw * 2);
         c.dmaW = wave * 1024;
     }
-    // fragment reads.  A (row mode): lane (i = l & 31, k half = l >> 5) reads chunk (2 step + (l >> 5)) ^ ((i >> 2) & 3)
-    // of row 128 wr + 32 it + i;  W (transposing): as in ver_wgrad.hip
+    // fragment reads.  32x32x16 -- A (row mode): lane (i = l & 31, k half = l >> 5) reads chunk (2 step + (l >> 5)) ^ swz_a(i)
+    // of row 128 wr + 32 it + i;  W (transposing): as in ver_wgrad.hip.  16x16x32 -- A: lane (i = l & 15, k-group g = l >> 4)
+    // reads chunk g ^ swz_a(i) of row 128 wr + 16 it + i;  W: group g reads rows 8 (g & 1) .. + 7 of slab g >> 1, lane c of
+    // it row c >> 2 (and + 4), chunk 2 q + ((c & 3) >> 1) of column tile q, half c & 1
     {
         const int lbase = (int)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
-        const int i = lane & 31, sw = (i >> 2) & 3;
-        c.offA0 = lbase + (128 * wr + i) * 64 + (((lane >> 5) ^ sw) << 4);
-        c.offA1 = c.offA0 ^ 32;
-        const int q = lane >> 4, cl = lane & 15;
-        const int lowch = (2 * (q & 1) + ((cl & 3) >> 1)) ^ (((cl >> 3) & 1) << 2);
-        c.offB0 = lbase + ((q >> 1) * 32 + (cl >> 2)) * 128 + lowch * 16 + (cl & 1) * 8 + wc * 1024;
-        c.offB1 = c.offB0 ^ 64;
+        if constexpr (kShape == 32) {
+            const int i = lane & 31;
+            c.offA0 = lbase + (128 * wr + i) * 64 + (((lane >> 5) ^ sh::swz_a(i & 15)) << 4);
+            c.offA1 = c.offA0 ^ 32;
+            const int q = lane >> 4, cl = lane & 15;
+            const int lowch = (2 * (q & 1) + ((cl & 3) >> 1)) ^ sh::swz_w(cl >> 2, q >> 1);
+            c.offB[0] = lbase + ((q >> 1) * 32 + (cl >> 2)) * 128 + lowch * 16 + (cl & 1) * 8 + wc * 1024;
+            c.offB[1] = c.offB[0] ^ 64;
+            c.offB[2] = c.offB[3] = 0;
+        } else {
+            const int i = lane & 15, g = lane >> 4;
+            c.offA0 = lbase + (128 * wr + i) * 64 + ((g ^ sh::swz_a(i)) << 4);
+            c.offA1 = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int ch = (2 * q + ((i & 3) >> 1)) ^ sh::swz_w(i >> 2, g & 1);
+                c.offB[q] = lbase + (g >> 1) * 8192 + (g & 1) * 4096 + (i >> 2) * 128 + ch * 16 + (i & 1) * 8 + wc * 1024;
+            }
+        }
     }
     TapLane tl = {};
+    TapWave ts = {};
     if constexpr (IMPL >= 0) {
         // this lane's two rows of the tile -> cells (b, zl, y, x); rows past M: no cell (every tap outside)
         const int prow = 32 * wave + (lane >> 2);
@@ -314,23 +442,29 @@ __global__ __launch_bounds__(512) void k_gemm_nn(GemmArgs p) {
         decode(row0 + prow + 16, tl.b2, tl.zl2, tl.y2, tl.x2);
         tl.pos1 = (tl.zl1 * p.t.H + tl.y1) * p.t.W + tl.x1;
         tl.pos2 = (tl.zl2 * p.t.H + tl.y2) * p.t.W + tl.x2;
-        tl.chunk = ((lane & 3) ^ ((prow >> 2) & 3)) * 16;
-        tl.tap = 0, tl.ch = 0;
-        tap_offsets<IMPL>(p.t, tl, ra);
+        tl.chunk = ((lane & 3) ^ sh::swz_a(prow & 15)) * 16;
+        // (the kernel's one parameter starts the kernel-argument block)
+        ts.tab = (const __attribute__((address_space(4))) unsigned*)((const __attribute__((address_space(4))) char*)
+                     __builtin_amdgcn_kernarg_segment_ptr() + offsetof(GemmArgs, t) + offsetof(TapArgs, desc));
+        unsigned d = desc_load(ts, 0);
+        desc_ready(d);
+        ts.next = desc_load(ts, min(1, p.t.ntaps - 1));
+        tap_begin<IMPL>(p.t, tl, ts, d, ra, rcst);
+        desc_ready(ts.next);
     }
-    f32x16 acc[4][2];
+    sh::acc_t acc[sh::NI][sh::NJ];
 #pragma unroll
-    for (int it = 0; it < 4; ++it)
+    for (int it = 0; it < sh::NI; ++it)
 #pragma unroll
-        for (int jt = 0; jt < 2; ++jt)
+        for (int jt = 0; jt < sh::NJ; ++jt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[it][jt][r] = 0.0f;
+            for (int r = 0; r < sh::NR; ++r) acc[it][jt][r] = 0.0f;
 
     int soA = 0, soW = 0;
     // prologue: phases 0 and 1 in flight, phase 0 landed
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-        request_a<IMPL>(lds + s * kStageBytes + c.dmaA, c, ra, rcst, soA, p.t, tl);
+        request_a<IMPL, true>(lds + s * kStageBytes + c.dmaA, c, ra, rcst, soA, p.t, tl, ts);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_void*)(lds + s * kStageBytes + 16384 + c.dmaW), 16, c.voW, soW, 0, 0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_void*)(lds + s * kStageBytes + 24576 + c.dmaW), 16, c.voW, soW + c.stepW, 0, 0);
         soW += 2 * c.stepW;
@@ -341,70 +475,71 @@ __global__ __launch_bounds__(512) void k_gemm_nn(GemmArgs p) {
 
     int s = 0;
     for (; s + kStages <= nphase; s += kStages) {
-        phase<0, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, rcst);
-        phase<1, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, rcst);
-        phase<2, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, rcst);
-        phase<3, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, rcst);
+        phase<0, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, ts, rcst);
+        phase<1, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, ts, rcst);
+        phase<2, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, ts, rcst);
+        phase<3, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, ts, rcst);
     }
     const int rem = nphase - s;
-    if (rem > 0) phase<0, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, rcst);
-    if (rem > 1) phase<1, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, rcst);
-    if (rem > 2) phase<2, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, rcst);
+    if (rem > 0) phase<0, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, ts, rcst);
+    if (rem > 1) phase<1, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, ts, rcst);
+    if (rem > 2) phase<2, IMPL>(lds, acc, c, ra, rw, soA, soW, p.t, tl, ts, rcst);
     if (wr == 0) __builtin_amdgcn_s_barrier();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
     if (p.S > 1) {
         // partial tile of this K slice -> workspace (fp32, [S][M][N]); bias and rounding happen in k_gemm_reduce
         float* out = p.ws + (long)split * p.M * p.N;
-        const long i0 = row0 + 128 * wr + 4 * (lane >> 5);
-        const int j0 = nt * kTile + 64 * wc + (lane & 31);
+        const long i0 = row0 + 128 * wr + sh::lane_row(lane);
+        const int j0 = nt * kTile + 64 * wc + (lane & (sh::TW - 1));
 #pragma unroll
-        for (int it = 0; it < 4; ++it)
+        for (int it = 0; it < sh::NI; ++it)
 #pragma unroll
-            for (int jt = 0; jt < 2; ++jt) {
-                const int j = j0 + 32 * jt;
+            for (int jt = 0; jt < sh::NJ; ++jt) {
+                const int j = j0 + sh::TW * jt;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const long i = i0 + 32 * it + (r & 3) + 8 * (r >> 2);
+                for (int r = 0; r < sh::NR; ++r) {
+                    const long i = i0 + sh::TW * it + sh::reg_row(r);
                     if (i < p.M && j < p.N) out[i * p.N + j] = acc[it][jt][r];
                 }
             }
         return;
     }
-    // C tile: register r of tile (it, jt) is row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31.  Buffer stores:
-    // one 32-bit lane offset + a scalar row offset per store; rows past M fall outside the range and are dropped, columns
-    // past N are sent there on purpose.
+    // C tile: register r of tile (it, jt) is row reg_row(r) + lane_row(lane), column lane & (TW - 1) of the tile (32x32x16:
+    // (r & 3) + 8 (r >> 2) + 4 (lane >> 5), lane & 31; 16x16x32: r + 4 (lane >> 4), lane & 15).  Buffer stores: one 32-bit lane
+    // offset + a scalar row offset per store; rows past M fall outside the range and are dropped, columns past N are sent
+    // there on purpose.
     __bf16* cb = p.C + row0 * p.ldc + (long)nt * kTile;
     const long cbytes = ((p.M - row0 - 1) * p.ldc + p.N - (long)nt * kTile) * 2;
     const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)cb, 0, (int)max(0L, min(cbytes, 0xFFFFFFFFL)), 0x00020000);
     const int ldc2 = (int)(p.ldc * 2);
-    const int vbase = (128 * wr + 4 * (lane >> 5)) * ldc2 + (64 * wc + (lane & 31)) * 2;
+    const int vbase = (128 * wr + sh::lane_row(lane)) * ldc2 + (64 * wc + (lane & (sh::TW - 1))) * 2;
     // implicit operand: + rowpos[row % P][j], the position-dependent constant part of the row's result (rows of a tile are
     // consecutive: one conditional subtraction per row instead of a division)
     const bool haspos = IMPL >= 0 && p.t.rowpos != nullptr;
-    const int pos0 = haspos ? (int)((row0 + 128 * wr + 4 * (lane >> 5)) % p.t.P) : 0;
+    const int pos0 = haspos ? (int)((row0 + 128 * wr + sh::lane_row(lane)) % p.t.P) : 0;
 #pragma unroll
-    for (int jt = 0; jt < 2; ++jt) {
-        const int j = nt * kTile + 64 * wc + 32 * jt + (lane & 31);
+    for (int jt = 0; jt < sh::NJ; ++jt) {
+        const int j = nt * kTile + 64 * wc + sh::TW * jt + (lane & (sh::TW - 1));
         const float bj = (p.bias && j < p.N) ? p.bias[j] : 0.0f;
-        const int vo = j < p.N ? vbase + 64 * jt : -2;
+        const int vo = j < p.N ? vbase + 2 * sh::TW * jt : -2;
 #pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            float add[16];
+        for (int it = 0; it < sh::NI; ++it) {
+            float add[sh::NR];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
+            for (int r = 0; r < sh::NR; ++r) {
                 add[r] = bj;
                 if (haspos) {
-                    int pp = pos0 + 32 * it + (r & 3) + 8 * (r >> 2);
+                    int pp = pos0 + sh::TW * it + sh::reg_row(r);
                     while (pp >= p.t.P) pp -= p.t.P;          // (at most once for P >= 256: the step's lattices have 450+)
-                    const long row = row0 + 128 * wr + 4 * (lane >> 5) + 32 * it + (r & 3) + 8 * (r >> 2);
+                    const long row = row0 + 128 * wr + sh::lane_row(lane) + sh::TW * it + sh::reg_row(r);
                     if (j < p.N && row < p.M) add[r] += p.t.rowpos[(long)pp * p.N + j];
                 }
             }
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
+            for (int r = 0; r < sh::NR; ++r) {
                 const __bf16 v = (__bf16)(acc[it][jt][r] + add[r]);
-                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(short, v), rc, vo, (32 * it + (r & 3) + 8 * (r >> 2)) * ldc2, 0);
+                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(short, v), rc, vo, (sh::TW * it + sh::reg_row(r)) * ldc2, 0);
             }
         }
     }
@@ -575,23 +710,20 @@ extern "C" int ver_gemm_nn_planes(const void* lattice, int layout, int B, int H,
     VER_REQUIRE((plane_elems == 0) == (tap_plane == nullptr) && plane_elems >= 0 && (plane_elems == 0 || (nplanes > 0 && nplanes <= 64 &&
                 plane_elems % 8 == 0)), VER_EINVAL, "ver_gemm_nn_planes: plane_elems, nplanes and tap_plane come together");
     p.t.plane_elems = plane_elems;
-    for (int i = 0; i < ntaps; ++i) {
-        VER_REQUIRE(!tap_plane || (tap_plane[i] >= 0 && tap_plane[i] < nplanes), VER_EINVAL, "ver_gemm_nn_planes: tap %d reads plane %d of %d", i,
-                    tap_plane ? tap_plane[i] : 0, nplanes);
-        p.t.pl[i] = (signed char)(tap_plane ? tap_plane[i] : 0);
-    }
     p.t.cst = (const __bf16*)cst;
     p.t.cst_bytes = cst ? (long)2 * H * W * ncst * cw * 2 : 0;
     p.t.CW = cw, p.t.ncst = ncst;
     for (int i = 0; i < ntaps; ++i) {
+        VER_REQUIRE(!tap_plane || (tap_plane[i] >= 0 && tap_plane[i] < nplanes), VER_EINVAL, "ver_gemm_nn_planes: tap %d reads plane %d of %d", i,
+                    tap_plane ? tap_plane[i] : 0, nplanes);
         const int dz = taps[3 * i], dy = taps[3 * i + 1], dx = taps[3 * i + 2];
         if (dz < 0) {
-            p.t.kind[i] = 1, p.t.dz[i] = (signed char)(-1 - dz), p.t.dy[i] = p.t.dx[i] = 0;
+            p.t.desc[i] = 0x80000000u | (unsigned)(-1 - dz) << 16;
             continue;
         }
         VER_REQUIRE((dz == 0 || dz == 2) && dy >= -64 && dy <= 64 && dx >= -64 && dx <= 64, VER_EINVAL,
                     "ver_gemm_nn_taps: tap %d = (%d, %d, %d): dz must be 0 or 2", i, dz, dy, dx);
-        p.t.kind[i] = 0, p.t.dz[i] = (signed char)dz, p.t.dy[i] = (signed char)dy, p.t.dx[i] = (signed char)dx;
+        p.t.desc[i] = (unsigned)(tap_plane ? tap_plane[i] : 0) << 22 | (unsigned)dz << 16 | (unsigned)(dy & 0xFF) << 8 | (unsigned)(dx & 0xFF);
     }
     hipError_t e = hipSuccess;
 #define VER_GEMM_TAPS(L)                                                                                                  \
