@@ -168,8 +168,8 @@ int ver_hits_from_mask(const uint8_t* bev_mask, int B, int Ncam, int Nq, int D,
  *             subnormals (absolute error < 6e-8); sample weights below ~6e-8 flush to zero.
  *             PRECISION: ~5e-4 of the partial sums (max |delta| 3.7e-3 at |slots| <= 1.2, 1e-3 relative L2 against
  *             fp32 accumulation of the same bf16 values; the north star's bf16 bound is 1e-2).
- *             VER_SCA_FWD_MATH=0 in the environment (read once per process) selects the exact form: bf16 tile
- *             unpacked per use, fp32 accumulation, <= 2e-5 like VER_F32.  Other shapes always use fp32 arithmetic.
+ *             The exact form of the contract is a VER_F32 value: fp32 tiles, fp32 accumulation, <= 2e-5.
+ *             Other shapes always use fp32 arithmetic.
  * flags: 0, or VER_SCA_ROWS_PREZEROED -- the caller has already zero-filled the rows `zero_list` names
  *   (`ver_sca_zero_rows(zero_list, zero_cnt, slots, B, Nq, heads*head_dim, side_stream)`, ordered before this call by
  *   an event): the fill depends on the hit table only, so it can run under the projections that precede the gather

@@ -1,5 +1,5 @@
-"""Helper of tests/test_hip_ops_gpu.py::test_sca_gather_launch_modes: the launch shape of ver_sca_forward is read
-from the environment once per process, so every mode runs in its own interpreter and writes its result to a file."""
+"""Helper of tests/test_hip_ops_gpu.py::test_sca_gather_samples_outside_the_map: a gather case at the 14x14 map with
+random offsets or the reference's initial ring of offsets."""
 import importlib
 import os
 import sys
@@ -32,14 +32,3 @@ def case(seed, B, grid, heads, hd, ring):
     else:
         offsets = torch.from_numpy((rng.standard_normal((B, nq, heads, 8, 2)) * 3.0).astype(np.float32)).cuda()
     return hip, hit, value, offsets, logits
-
-
-if __name__ == '__main__':
-    out = sys.argv[1]
-    res = {}
-    for name, args in (('vocc_f32', (5, 3, (4, 15, 15), 8, 96, False)), ('vocc_ring', (6, 3, (4, 15, 15), 8, 96, True)),
-                       ('small', (7, 2, (3, 7, 6), 2, 32, False))):
-        hip, hit, value, offsets, logits = case(*args)
-        res[name + '_f32'] = hip.sca_gather(value, offsets, logits, hit, 14, 14).cpu().numpy()
-        res[name + '_bf16'] = hip.sca_gather(value.bfloat16(), offsets, logits, hit, 14, 14).cpu().numpy()
-    np.savez(out, **res)

@@ -16,7 +16,8 @@
 // with three or more the last bit may vary with the order of the adds.  Voxels seen by no camera get exact zeros.
 //
 // On bf16 tiles k_sca_fwd_cs converts the staged tile to fp16 in LDS and accumulates the <= 8 points of a (voxel, head,
-// corner) with v_pk_fma_f16 (VER_SCA_FWD_MATH=0: bf16 tile unpacked to fp32 per use, exact fp32 accumulation).
+// corner) with v_pk_fma_f16; fp32 tiles are gathered in fp32 throughout (the exact form of the contract is an fp32 value).
+// Every launch shape is a constant named in the launcher that uses it: nothing here reads the environment.
 //
 // Backward (ver_sca_backward), by shape:
 //   * bf16 tiles, 8 points, head_dim % 32 == 0, tile + buffers <= 160 KB  ->  k_sca_bwd_mm: ONE kernel on the matrix
@@ -29,7 +30,6 @@
 //     atomics in LDS; the order of a row's events inside the sort is not fixed, so d(value) may differ in the last
 //     bit run to run, as the reference's CUDA backward does);
 //   * head_dim < 32 or large maps  ->  k_sca_bwd, a single LDS-atomic kernel.
-#include <cstdlib>
 #include <type_traits>
 #include "ver_common.h"
 
@@ -327,10 +327,10 @@ __device__ __forceinline__ void stage_wait() {
 // ------------------------------------------------------------------------------------------
 // Forward.  One workgroup of 16 waves per (viewpoint, camera, head group [, list chunk]) walks
 // its heads with a double-buffered LDS tile:
-//   * the last kFwdLoaders waves are LOADERS: they only issue LDS-DMA (global_load_lds_dwordx4)
-//     for the next head's 14x14xHD tile while the other waves work on the current one, so after
-//     the first tile the HBM stream of the value tensor hides behind compute (one barrier / head);
-//   * the other waves are CONSUMERS.  A wave takes 4 voxels per iteration, one per 16-lane DPP row,
+//   * every wave issues its share of the LDS-DMA (global_load_lds_dwordx4) for the next head's
+//     14x14xHD tile before it works on the current one, so after the first tile the HBM stream of
+//     the value tensor hides behind compute (one barrier / head);
+//   * a wave takes 4 voxels per iteration, one per 16-lane DPP row,
 //     with two lane roles inside a row so that per-sample arithmetic is done once, not once per
 //     channel lane:
 //       phase A  lane = (point, corner subset): loads ITS logit / offset / uv, softmax over the P
@@ -344,11 +344,6 @@ __device__ __forceinline__ void stage_wait() {
 // LDS.  Rows of voxels seen by exactly one camera are plain stores; rows seen by several cameras
 // were zeroed by k_zero_rows and are accumulated with fp32 atomics (2 addends commute exactly, so
 // results stay bitwise reproducible as long as no voxel is seen by more than two cameras).
-#ifndef VER_FWD_LOADERS
-#define VER_FWD_LOADERS 0
-#endif
-constexpr int kFwdLoaders = VER_FWD_LOADERS;   // 0: every wave issues its share of the next tile's LDS-DMA
-
 #ifdef VER_DEBUG_TIMELINE
 // timeline of 32 probe workgroups of k_sca_fwd_cs (scratch/r04/timeline_cs.py; build with -DVER_DEBUG_TIMELINE):
 // g_tl[probe][wave][event] = s_memtime
@@ -484,7 +479,6 @@ __global__ __launch_bounds__(kFwdThreads) void k_sca_fwd(
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int CPL = HD / G;
     const int nwaves = (int)(blockDim.x >> 6);                         // 16 (or 8 with two workgroups per CU)
-    const int NCONS = nwaves - kFwdLoaders;                            // consumer waves
     const int Nk = mh * mw;
     const size_t tile_elems = (size_t)Nk * HD;
     VT* tiles = reinterpret_cast<VT*>(smem);
@@ -504,34 +498,27 @@ __global__ __launch_bounds__(kFwdThreads) void k_sca_fwd(
     const VT* vown = value + ((size_t)b * Ncam + c) * Nk * rstride;   // this camera, head 0
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const bool loader = kFwdLoaders > 0 && wave >= NCONS;
-    const int dma_wave = kFwdLoaders > 0 ? wave - NCONS : wave;
-    const int kDmaWaves = kFwdLoaders > 0 ? kFwdLoaders : nwaves;
-    const bool issues_dma = kFwdLoaders == 0 || loader;
     const int* list = vis_list + ((size_t)b * Ncam + c) * Nq;
     const float inv_w = 1.0f / (float)mw, inv_h = 1.0f / (float)mh;
 
-    if (issues_dma && nbuf == 2) stage_tile<HD, VT>(tiles, vown + (size_t)h0 * HD, rstride, Nk, dma_wave, kDmaWaves);
+    if (nbuf == 2) stage_tile<HD, VT>(tiles, vown + (size_t)h0 * HD, rstride, Nk, wave, nwaves);
 
     for (int hh = 0; hh < heads_per; ++hh) {
         const int h = h0 + hh;
         const int cur = nbuf == 2 ? (hh & 1) : 0;
         VT* tile = tiles + cur * tile_elems;
         if (nbuf == 1) {
-            __syncthreads();                          // consumers are done with the previous head
-            if (issues_dma) stage_tile<HD, VT>(tile, vown + (size_t)h * HD, rstride, Nk, dma_wave, kDmaWaves);
+            __syncthreads();                          // everyone is done with the previous head
+            stage_tile<HD, VT>(tile, vown + (size_t)h * HD, rstride, Nk, wave, nwaves);
         }
-        if (issues_dma) __builtin_amdgcn_s_waitcnt(0);    // this wave's share of the head's tile has landed
+        __builtin_amdgcn_s_waitcnt(0);                // this wave's share of the head's tile has landed
         __syncthreads();
-        if (issues_dma && nbuf == 2 && hh + 1 < heads_per)
-            stage_tile<HD, VT>(tiles + (cur ^ 1) * tile_elems, vown + (size_t)(h + 1) * HD, rstride, Nk, dma_wave,
-                               kDmaWaves);
-        if (loader) continue;
+        if (nbuf == 2 && hh + 1 < heads_per)
+            stage_tile<HD, VT>(tiles + (cur ^ 1) * tile_elems, vown + (size_t)(h + 1) * HD, rstride, Nk, wave, nwaves);
 
-        // ------------------------------------------------------------ consumers
         if constexpr (G == 16) {
             constexpr int LPP = 16 / P, CPN = 4 / LPP;
-            const int STEP = NCONS * 4;
+            const int STEP = nwaves * 4;
             const int row = lane >> 4, lr = lane & 15;
             const int ap = lr / LPP, asub = lr % LPP;      // phase A: point, corner subset
             const int ad = (D == 1) ? 0 : (ap % D);
@@ -611,7 +598,7 @@ __global__ __launch_bounds__(kFwdThreads) void k_sca_fwd(
             // narrow heads (HD < 32, test sizes): plain per-lane path, G lanes per voxel
             constexpr int VPW = VER_WAVE / G;
             const int sub = lane / G, gl = lane % G;
-            for (int i = start + wave * VPW + sub; i < end; i += NCONS * VPW) {
+            for (int i = start + wave * VPW + sub; i < end; i += nwaves * VPW) {
                 const int nb = list[i];
                 const unsigned mb = vis[(size_t)b * Nq + nb];
                 const size_t qh = ((size_t)b * Nq + nb) * heads + h;
@@ -682,15 +669,15 @@ __device__ __forceinline__ void permlane16_swap(float& a, float& b) {
 __device__ float g_sca_dummy_row[256 * 256];        // one 1-KiB slice per (blockIdx & 255): no chip-wide hot line
 
 // ------------------------------------------------------------------------------------------
-// Forward, corner-slot kernel with a merged work list, sample compaction and (optionally) streaming loader waves.
+// Forward, corner-slot kernel with a merged work list and sample compaction.
 //
-// A workgroup walks a contiguous range of (viewpoint, camera, chunk, head group) units, one (camera, head) tile
-// at a time:
-//   nload > 0  persistent form: the last `nload` waves only stream tiles (LDS-DMA of tile i+1 while the consumers
-//              work on tile i; two tile buffers, one barrier per tile);
-//   nload == 0 every wave stages its share of the tile, then all of them gather from it (one buffer; several
-//              workgroups per CU overlap each other's staging).
-// The consumer waves split a tile's voxel PAIRS into contiguous ranges over the merged list
+// A workgroup owns ONE (viewpoint, camera, chunk, head group) unit and walks its heads one (camera, head) tile at a
+// time: every wave stages its share of the tile, then all of them gather from it (one buffer; several workgroups per CU
+// overlap each other's staging).  Measured and dropped (docs/HISTORY.md section 3.1): loader waves that stream tiles
+// through two buffers for a persistent workgroup, and several units per workgroup -- one 16-wave workgroup per CU cannot
+// hold more waves than four small ones, and its tiles split into 4-5 pairs per wave with a second, nearly empty phase-A
+// pass.
+// The waves split a tile's voxel PAIRS into contiguous ranges over the merged list
 // [voxels only this camera sees, padded to a whole pair | voxels shared with other cameras]: a pair is either all
 // plain stores or all atomic adds (wave-uniform).  Voxel ids / visibility of a unit are fetched once for all its
 // heads, and the first operands of a tile are requested before the tile barrier.
@@ -698,15 +685,15 @@ __device__ float g_sca_dummy_row[256 * 256];        // one 1-KiB slice per (bloc
 // COMPACTS the live samples of a voxel to the front of its record row, and a pair only walks
 // max(live samples of its two voxels) points -- with the reference's initial ring of offsets (1..8 px on a 14-px
 // map, spatial_cross_attention.py:255-270) more than a third of the samples are outside.
-// MATH (bf16 tiles only): how the gather multiplies a tile row by its weight.
-//   0  the tile stays bf16 in LDS; every use unpacks to fp32 (v_and / v_lshlrev) and accumulates with v_pk_fma_f32
-//   2  each wave converts the chunks it staged to fp16 IN PLACE (exact for bf16 values with |x| in [6.1e-5, 65504]:
-//      8 mantissa bits fit in 11; RTZ saturates above and truncates into the subnormals below, abs. error < 6e-8),
-//      weights travel as packed fp16 pairs, and the <= 8 points of a (voxel, head, corner) are accumulated with
-//      v_pk_fma_f16 -- two channels per instruction, no unpack; the corner fold runs on the packed sums, everything
+// How the gather multiplies a tile row by its weight follows from the value type:
+//   fp32 tiles  fp32 arithmetic throughout (v_pk_fma_f32);
+//   bf16 tiles  each wave converts the chunks it staged to fp16 IN PLACE (exact for bf16 values with |x| in
+//      [6.1e-5, 65504]: 8 mantissa bits fit in 11; RTZ saturates above and truncates into the subnormals below, abs.
+//      error < 6e-8), weights travel as packed fp16 pairs, and the <= 8 points of a (voxel, head, corner) are accumulated
+//      with v_pk_fma_f16 -- two channels per instruction, no unpack; the corner fold runs on the packed sums, everything
 //      after it (camera sum, division) in fp32.  Error ~5e-4 of the partial sums (bf16 bound of the north star: 1e-2).
-//   (1 = fp16 tile with fp32 accumulation: the compiler turns it into v_cvt_f32_f16 + v_pk_fma_f32, as many
-//    instructions as mode 0 -- measured 3 % slower, 437 vs 424 us per launch; not dispatched.)
+//   (Measured and dropped: the bf16 tile unpacked to fp32 per use, and an fp16 tile with fp32 accumulation -- the compiler
+//    turns that into v_cvt_f32_f16 + v_pk_fma_f32, as many instructions as the unpack: 3 % slower, 437 vs 424 us per launch.)
 // HM (head-major value, head_major_views > 0): the tile is one contiguous block of HBM and is staged as it lies, ROW-major in
 // LDS (a tile row = HD elements); the corner rows (r, r+1, r+14, r+15) of a 14-wide map of 192-byte rows still fall on four
 // disjoint 64-byte bank groups (0, 192, 128, 64 mod 256; profiles/r02_ubench_lds.txt), so the gather stays conflict free.
@@ -715,29 +702,24 @@ __device__ float g_sca_dummy_row[256 * 256];        // one 1-KiB slice per (bloc
 // instructions (35 M per 192-viewpoint launch in round 3's counters), executed by every wave in front of its first DMA request.
 // The host passes floor(2^32 / d) + 1 per divisor: one s_mul_hi_u32, exact for n < 2^32 / d (checked by the launcher).
 struct CsMagic {
-    unsigned hsplit, nchunks, ncam, hper, ncons;
+    unsigned hsplit, nchunks, ncam, nwaves;
 };
 __host__ __device__ __forceinline__ unsigned cs_magic(int d) { return d > 1 ? (unsigned)(0x100000000ull / (unsigned)d) + 1u : 0u; }
 __device__ __forceinline__ int cs_div(int n, int d, unsigned m) { return d == 1 ? n : (int)__umulhi((unsigned)n, m); }
 
-// ONE: the launch shape that ships (one tile per workgroup, no loader waves, one voxel chunk) as compile-time constants --
-// the unit / head loops, the loader path and their registers (63 spilled SGPRs in the general form) fold away.
-#ifndef VER_CS_DMA_AUX
-#define VER_CS_DMA_AUX 0        // cache policy bits of the reference-layout tile DMA (experiment hook; 2 = non-temporal: measured no better)
-#endif
-template <int HD, typename VT, int NKT, int MATH = 0, bool HM = false, bool ONE = false>
+// ONE: the launch shape that ships (one tile per workgroup, one voxel chunk) as compile-time constants -- the head loop and
+// its registers fold away.
+template <int HD, typename VT, int NKT, bool HM = false, bool ONE = false>
 __global__ __launch_bounds__(1024) void k_sca_fwd_cs(
     const VT* __restrict__ value, const float* __restrict__ offs, const float* __restrict__ logits,
     const float* __restrict__ uv, const uint8_t* __restrict__ vis, const int* __restrict__ fwd_list,
     const int* __restrict__ fwd_cnt, float* slots, int Ncam, int Nq, int D, int heads, int mh, int mw,
-    int nchunks_a, int chunk, int hsplit, int units_total, int units_per_wg_a, int nload_a, int head_major_views, int reverse,
-    int heads_per_a, CsMagic mg) {
-    const int nchunks = ONE ? 1 : nchunks_a, units_per_wg = ONE ? 1 : units_per_wg_a, nload = ONE ? 0 : nload_a;
-    const int heads_per = ONE ? 1 : heads_per_a;
-    // reverse: walk the units from the LAST viewpoint to the first.  The value tensor (347 MB at 192 viewpoints) and the
+    int nchunks_a, int chunk, int hsplit, int units_total, int head_major_views, int heads_per_a, CsMagic mg) {
+    const int nchunks = ONE ? 1 : nchunks_a, heads_per = ONE ? 1 : heads_per_a;
+    // The units are walked from the LAST viewpoint to the first.  The value tensor (347 MB at 192 viewpoints) and the
     // offsets / logits were written just before this launch, in ascending row order, through a 256-MB memory-side cache:
     // reading them back in the SAME order finds the oldest lines already evicted, reading in the opposite order starts with
-    // the ones still resident.
+    // the ones still resident.  (Measured a tie with the forward walk at the vocc size; kept.)
     // head_major_views: 0 = value in the reference's layout [B, Ncam, Nk, heads, HD] (a tile row is HD elements inside a
     // heads*HD-wide token row); B > 0 = head-major [heads, B, Ncam, Nk, HD]: a (camera, head) tile is ONE contiguous block
     // of HBM -- every 1-KB LDS-DMA instruction then covers 8 whole 128-byte lines instead of ~11 partial ones, and no line
@@ -749,11 +731,8 @@ __global__ __launch_bounds__(1024) void k_sca_fwd_cs(
     constexpr unsigned RB = (HM ? HD : 32) * sizeof(VT);            // bytes between tile rows in LDS
     constexpr int CPR = 32 * sizeof(VT) / 16, EPC = 16 / sizeof(VT);
     static_assert(HD % 32 == 0, "8 lanes x vectors of 4 channels");
-    static_assert(MATH == 0 || !F32, "the fp16 modes are for bf16 tiles");
     typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
     const int nwaves = (int)(blockDim.x >> 6);
-    const int ncons = nwaves - nload;
-    const int nbuf = nload > 0 ? 2 : 1;
     const int Nk = NKT ? NKT : mh * mw;
     const unsigned plane = HM ? 32u * (unsigned)sizeof(VT) : (unsigned)Nk * RB;      // bytes between a row's 32-channel groups
     const unsigned tile_bytes = ((unsigned)(NV * Nk * 32 * sizeof(VT)) + 15u) & ~15u;
@@ -764,36 +743,28 @@ __global__ __launch_bounds__(1024) void k_sca_fwd_cs(
     // 128-byte lines of the offsets / logits / value rows, and now meet them in ONE L2 instead of eight.
     const int wg_per_xcd = (int)(gridDim.x >> 3);                 // the grid is a multiple of 8
     const int wg = (int)(blockIdx.x & 7) * wg_per_xcd + (int)(blockIdx.x >> 3);
-    const int u0 = wg * units_per_wg, u1 = min(u0 + units_per_wg, units_total);
-    const int ntiles = (u1 - u0) * heads_per;
-    if (ntiles <= 0) return;
+    if (wg >= units_total) return;                                // the grid is padded to a multiple of 8
     VER_TL(0);
+    // this workgroup's unit, last viewpoint first
+    const int un = units_total - 1 - wg;
+    const int rq = cs_div(un, hsplit, mg.hsplit), hs = un - rq * hsplit;
+    const int bc = cs_div(rq, nchunks, mg.nchunks), ck = rq - bc * nchunks;
+    const int b = cs_div(bc, Ncam, mg.ncam), c = bc - b * Ncam;
+    const int h0 = hs * heads_per;
 
-    // Tile staging.  A lone loader wave runs its address arithmetic as one dependent chain, so the per-DMA work is a
-    // handful of instructions: the lane's (plane, row) position advances incrementally and the tile's base pointer
-    // is wave-uniform.  (Two integer divisions per DMA cost a loader wave 23 k cycles per 75-KB tile.)
-    const int dma_wave = nload ? wave - ncons : wave, dma_waves = nload ? nload : nwaves;
+    // Tile staging.  The per-DMA work is a handful of instructions: the lane's (plane, row) position advances
+    // incrementally and the tile's base pointer is wave-uniform.
     const int total_chunks = NV * Nk * CPR;
-    const int rows_per_step = 64 * dma_waves / CPR;                // plane rows covered by one step of all DMA waves
-    const int q_first = dma_wave * 64 + lane;
+    const int rows_per_step = 64 * nwaves / CPR;                   // plane rows covered by one step of all waves
+    const int q_first = wave * 64 + lane;
     const int jc = q_first % CPR;
     const int i_first = (q_first / CPR) / Nk, k_first = (q_first / CPR) - i_first * Nk;
-    auto stage = [&](int i) {
-        const int iu = cs_div(i, heads_per, mg.hper);
-        int r = u0 + iu;
-        if (reverse) r = units_total - 1 - r;
-        const int rq = cs_div(r, hsplit, mg.hsplit), hs = r - rq * hsplit;
-        r = cs_div(rq, nchunks, mg.nchunks);
-        const int b = cs_div(r, Ncam, mg.ncam), c = r - b * Ncam;
-        const int h = hs * heads_per + (i - iu * heads_per);
-        VT* dst = reinterpret_cast<VT*>(smem + (nbuf == 2 ? (i & 1) : 0) * tile_bytes);
-#ifdef VER_ABL_NODMA
-        if (i >= 0) return;
-#endif
+    auto stage = [&](int h) {
+        VT* dst = reinterpret_cast<VT*>(smem);
         if constexpr (HM) {
             // chunk q of the tile is chunk q of the block: no address arithmetic beyond the lane offset
             const VT* src = value + ((((size_t)h * head_major_views + b) * Ncam + c) * Nk) * HD;
-            for (int q0 = dma_wave * 64; q0 < total_chunks; q0 += 64 * dma_waves) {
+            for (int q0 = wave * 64; q0 < total_chunks; q0 += 64 * nwaves) {
                 if (q0 + lane < total_chunks)
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)(q0 + lane) * EPC),
                                                      (__attribute__((address_space(3))) void*)(dst + (size_t)q0 * EPC), 16, 0, 2);
@@ -802,11 +773,12 @@ __global__ __launch_bounds__(1024) void k_sca_fwd_cs(
         }
         const VT* src = value + ((size_t)b * Ncam + c) * Nk * rstride + (size_t)h * HD + jc * EPC;
         int pi = i_first, pk = k_first;
-        for (int q0 = dma_wave * 64; q0 < total_chunks; q0 += 64 * dma_waves) {
+        for (int q0 = wave * 64; q0 < total_chunks; q0 += 64 * nwaves) {
             if (q0 + lane < total_chunks) {
                 const VT* g = src + (size_t)pk * rstride + pi * 32;
+                // (cache policy 0; 2 = non-temporal measured no better for the reference layout)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                 (__attribute__((address_space(3))) void*)(dst + (size_t)q0 * EPC), 16, 0, VER_CS_DMA_AUX);
+                                                 (__attribute__((address_space(3))) void*)(dst + (size_t)q0 * EPC), 16, 0, 0);
             }
             pk += rows_per_step;
             while (pk >= Nk) {
@@ -817,37 +789,16 @@ __global__ __launch_bounds__(1024) void k_sca_fwd_cs(
     };
 
     // bf16 -> fp16 in place, by the wave that staged the chunk (its own s_waitcnt covers the DMA): no extra barrier
-    auto to_f16 = [&](int i) {
-#ifdef VER_ABL_NOCONV
-        return;
-#endif
-        if constexpr (MATH != 0) {
-            const unsigned dst = (unsigned)(uintptr_t)(lds_byte*)reinterpret_cast<const unsigned char*>(smem) +
-                                 (nbuf == 2 ? (unsigned)(i & 1) : 0u) * tile_bytes;
-#ifdef VER_CS_CONV_SERIAL
-            for (int q0 = dma_wave * 64; q0 < total_chunks; q0 += 64 * dma_waves) {
-                if (q0 + lane < total_chunks) {
-                    const unsigned a = dst + (unsigned)(q0 + lane) * 16u;
-                    u32x4_t w = *lds_ptr<u32x4_t>(a);
-                    u32x4_t o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const unsigned x = e == 0 ? w.x : e == 1 ? w.y : e == 2 ? w.z : w.w;
-                        const auto hh = __builtin_amdgcn_cvt_pkrtz(__uint_as_float(x << 16), __uint_as_float(x & 0xffff0000u));
-                        const unsigned r = __builtin_bit_cast(unsigned, hh);
-                        if (e == 0) o.x = r; else if (e == 1) o.y = r; else if (e == 2) o.z = r; else o.w = r;
-                    }
-                    *lds_ptr_mut<u32x4_t>(a) = o;
-                }
-            }
-#else
+    auto to_f16 = [&]() {
+        if constexpr (!F32) {
+            const unsigned dst = (unsigned)(uintptr_t)(lds_byte*)reinterpret_cast<const unsigned char*>(smem);
             // five chunks per lane in flight: the serial form (read, wait, convert, write per chunk) ran ten dependent LDS
             // round trips per tile -- ~10 k cycles of every workgroup's ~60 k-cycle prologue (scratch/r04/timeline_cs.py).
             // Reads past the end are clamped to the last chunk (which its owner may already have converted: the value is
             // dropped), only the store is predicated.
             constexpr int kBatch = 5;
-            const int step = 64 * dma_waves;
-            for (int q0 = dma_wave * 64 + lane; q0 < total_chunks; q0 += kBatch * step) {
+            const int step = 64 * nwaves;
+            for (int q0 = wave * 64 + lane; q0 < total_chunks; q0 += kBatch * step) {
                 u32x4_t w[kBatch];
 #pragma unroll
                 for (int k = 0; k < kBatch; ++k)
@@ -865,27 +816,9 @@ __global__ __launch_bounds__(1024) void k_sca_fwd_cs(
                     if (q0 + k * step < total_chunks) *lds_ptr_mut<u32x4_t>(dst + (unsigned)(q0 + k * step) * 16u) = o;
                 }
             }
-#endif
         }
     };
 
-    if (nload > 0 && wave >= ncons) {
-        // ------------------------------------------------------------ loader waves: stream the tiles
-        stage(0);
-        for (int i = 0; i < ntiles; ++i) {
-            if (i < 7) VER_TL(8 * i + 10);
-            __builtin_amdgcn_s_waitcnt(0);            // this wave's share of tile i has landed
-            if (i < 7) VER_TL(8 * i + 11);
-            to_f16(i);
-            if (i < 7) VER_TL(8 * i + 12);
-            __syncthreads();                          // tile i complete; the consumers are done with tile i - 1
-            if (i < 7) VER_TL(8 * i + 13);
-            if (i + 1 < ntiles) stage(i + 1);
-        }
-        return;
-    }
-
-    // ---------------------------------------------------------------- consumer waves
     const int s4 = lane >> 4, v2 = (lane >> 3) & 1, l8 = lane & 7;   // phase A: pair of the iteration, voxel of the pair, point
     const int half = lane >> 5, rho = (lane >> 4) & 1, sigma = (lane >> 3) & 1;
     const int ad = (D == 1) ? 0 : (l8 % D);
@@ -893,7 +826,7 @@ __global__ __launch_bounds__(1024) void k_sca_fwd_cs(
     const unsigned smem_lds = (unsigned)(uintptr_t)(lds_byte*)reinterpret_cast<const unsigned char*>(smem);
     // records {weight, row offset} of a voxel pair: [voxel of the pair][corner][slot], 8 B each: a corner slot reads
     // its 8 sample slots as four conflict-free ds_read_b128 (corner rows are 64 B = 16 banks apart)
-    const unsigned rec_wave = smem_lds + (unsigned)nbuf * tile_bytes + (unsigned)wave * 512u;
+    const unsigned rec_wave = smem_lds + tile_bytes + (unsigned)wave * 512u;
     const unsigned rec_wr0 = rec_wave + (unsigned)v2 * 256u;                                      // + slot * 8 + corner * 64
     const unsigned rec_rd = rec_wave + (unsigned)half * 256u + (unsigned)((lane >> 3) & 3) * 64u;
     const unsigned lane_off = (unsigned)l8 * (F32 ? 16u : 8u);
@@ -902,330 +835,274 @@ __global__ __launch_bounds__(1024) void k_sca_fwd_cs(
         float lg;
         float2 of, u;
     };
-    int ti = 0;                                       // tile counter of this workgroup
-#ifndef VER_CS_NO_DMA_FIRST
     // The first tile's LDS-DMA depends on nothing but the block index: it goes out before the counts, the voxel ids and
     // the first samples are fetched (three dependent memory round trips that used to run IN FRONT of it).
-    if (nload == 0) stage(0);
-#endif
-#ifndef VER_CS_NO_PRIO
+    stage(h0);
     // a new workgroup's waves are the youngest of their SIMDs and lose every issue arbitration against the older waves'
     // gather loops: the prologue (requests, tile conversion) runs at raised priority, the gather itself at the default
     __builtin_amdgcn_s_setprio(3);
-#endif
-    for (int un = u0; un < u1; ++un) {
-        int r = reverse ? units_total - 1 - un : un;
-        const int rq = cs_div(r, hsplit, mg.hsplit), hs = r - rq * hsplit;
-        r = cs_div(rq, nchunks, mg.nchunks);
-        const int ck = rq - r * nchunks;
-        const int b = cs_div(r, Ncam, mg.ncam), c = r - b * Ncam;
-        const int h0 = hs * heads_per;
-        const int n_single = fwd_cnt[(b * Ncam + c) * 2], n_multi = fwd_cnt[(b * Ncam + c) * 2 + 1];
-        const int w_start = ck * chunk;
-        const int s_n = max(0, min(n_single - w_start, chunk)), m_n = max(0, min(n_multi - w_start, chunk));
-        const int s_n2 = (s_n + 1) & ~1, s_pairs = s_n2 >> 1;
-        const int TP = s_pairs + ((m_n + 1) >> 1);
-        const int p_lo = cs_div(wave * TP, ncons, mg.ncons), p_hi = cs_div((wave + 1) * TP, ncons, mg.ncons);   // < 2^28: TP < 2^24
-        const int iters = (p_hi - p_lo + 3) >> 2;
-        const int* list = fwd_list + ((size_t)b * Ncam + c) * Nq;
-        // list entry of this lane in wave iteration `it`; dead entries (pad, odd tail, pairs of other waves) return
-        // -(id of a live voxel of the same region) - 1
-        auto load_id = [&](int it) -> int {
-            const int pp = min(p_lo + 4 * it + s4, TP - 1);
-            const int e = 2 * pp + v2;
-            const bool multi = e >= s_n2;
-            const int idx = multi ? e - s_n2 : e;
-            const int lim = multi ? m_n : s_n;
-            const int pos = multi ? (Nq - 1 - w_start - min(idx, lim - 1)) : (w_start + min(idx, lim - 1));
-            const int n = list[pos];
-            return (idx < lim && p_lo + 4 * it + s4 < p_hi) ? n : -n - 1;
-        };
-        int un0 = -1, un1 = -1, un2 = -1;
-        if (iters > 0) {
-            un0 = load_id(0);
-            un1 = load_id(1);
-            un2 = load_id(2);
+    const int n_single = fwd_cnt[(b * Ncam + c) * 2], n_multi = fwd_cnt[(b * Ncam + c) * 2 + 1];
+    const int w_start = ck * chunk;
+    const int s_n = max(0, min(n_single - w_start, chunk)), m_n = max(0, min(n_multi - w_start, chunk));
+    const int s_n2 = (s_n + 1) & ~1, s_pairs = s_n2 >> 1;
+    const int TP = s_pairs + ((m_n + 1) >> 1);
+    const int p_lo = cs_div(wave * TP, nwaves, mg.nwaves), p_hi = cs_div((wave + 1) * TP, nwaves, mg.nwaves);   // < 2^28: TP < 2^24
+    const int iters = (p_hi - p_lo + 3) >> 2;
+    const int* list = fwd_list + ((size_t)b * Ncam + c) * Nq;
+    // list entry of this lane in wave iteration `it`; dead entries (pad, odd tail, pairs of other waves) return
+    // -(id of a live voxel of the same region) - 1
+    auto load_id = [&](int it) -> int {
+        const int pp = min(p_lo + 4 * it + s4, TP - 1);
+        const int e = 2 * pp + v2;
+        const bool multi = e >= s_n2;
+        const int idx = multi ? e - s_n2 : e;
+        const int lim = multi ? m_n : s_n;
+        const int pos = multi ? (Nq - 1 - w_start - min(idx, lim - 1)) : (w_start + min(idx, lim - 1));
+        const int n = list[pos];
+        return (idx < lim && p_lo + 4 * it + s4 < p_hi) ? n : -n - 1;
+    };
+    int un0 = -1, un1 = -1, un2 = -1;
+    if (iters > 0) {
+        un0 = load_id(0);
+        un1 = load_id(1);
+        un2 = load_id(2);
+    }
+    for (int hh = 0; hh < heads_per; ++hh) {
+        const int h = h0 + hh;
+        if (hh) {
+            __syncthreads();                  // everyone is done with the previous tile
+            stage(h);
         }
-        for (int hh = 0; hh < heads_per; ++hh, ++ti) {
-            const int h = h0 + hh;
-            if (nload == 0) {
-#ifndef VER_CS_NO_DMA_FIRST
-                if (ti) {
-                    __syncthreads();                  // everyone is done with the previous tile
-                    stage(ti);
-                }
-#else
-                if (ti) __syncthreads();              // everyone is done with the previous tile
-                stage(ti);
-#endif
-            }
-            // per-tile WAVE-UNIFORM base pointers; a lane's address is base + 32-bit byte offset (one 24-bit multiply-add),
-            // which the memory instructions take as SGPR base + VGPR offset -- no 64-bit VALU arithmetic per access
-            const char* lg_base = reinterpret_cast<const char*>(logits + ((size_t)b * Nq * heads + h) * P);
-            const char* of_base = reinterpret_cast<const char*>(offs + ((size_t)b * Nq * heads + h) * P * 2);
-            const char* uv_base = reinterpret_cast<const char*>(uv + ((size_t)b * Ncam + c) * Nq * D * 2);
-            const uint8_t* vis_base = vis + (size_t)b * Nq;
-            char* out_base = reinterpret_cast<char*>(slots + ((size_t)b * Nq * heads + h) * HD);
-            const unsigned hp4 = (unsigned)(heads * P * 4), hhd4 = (unsigned)(heads * HD * 4), d8 = (unsigned)(D * 8);
-            auto load_sample = [&](int n) -> Sample {
-                Sample sm;
-                const unsigned nn = (unsigned)(n < 0 ? -n - 1 : n);          // < 2^24 voxels (checked by the host wrapper)
-                sm.m = (unsigned)vis_base[nn];           // raw: a dead entry's mask is cleared where the record is used
-                sm.lg = *reinterpret_cast<const float*>(lg_base + (__umul24(nn, hp4) + (unsigned)l8 * 4u));
-                sm.of = *reinterpret_cast<const float2*>(of_base + (__umul24(nn, hp4) * 2u + (unsigned)l8 * 8u));
-                sm.u = *reinterpret_cast<const float2*>(uv_base + (__umul24(nn, d8) + (unsigned)ad * 8u));
-                return sm;
-            };
-            int n0 = un0, n1 = un1, n2 = un2;
-            Sample s0 = {};
-            if (iters > 0) s0 = load_sample(n0);      // requested before the tile barrier: the latency hides behind it
-            VER_TL(1);
-            if (nload == 0) {
-                __builtin_amdgcn_s_waitcnt(0);        // this wave's share of the tile has landed
-                VER_TL(2);
-                to_f16(ti);
-            }
-            VER_TL(3);
-            if (nload > 0 && ti < 7) VER_TL(8 * ti + 14);
-            __syncthreads();                          // tile ti is complete
-#ifndef VER_CS_NO_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
-            VER_TL(4);
-            if (nload > 0 && ti < 7) VER_TL(8 * ti + 15);
-            const unsigned base4 = smem_lds + (nbuf == 2 ? (unsigned)(ti & 1) * tile_bytes : 0u) + lane_off;
-#ifndef VER_CS_NO_PRESTORE_WAIT
-            __builtin_amdgcn_s_waitcnt(0x0f70);       // the first iteration's operands (requested before the tile barrier)
-#endif
-            // operands: voxel ids two wave iterations ahead, sample records one ahead (all loads and stores of the loop
-            // are unconditional, so the compiler's vmcnt waits never have to drain the young output stores)
-            for (int it = 0; it < iters; ++it) {
-                const Sample s1 = load_sample(n1);
-                const int n3 = load_id(it + 3);
-                // ---------------- phase A: lane = sampling point l8 of voxel (s4, v2)
-                const unsigned m = n0 < 0 ? 0u : s0.m;
-                float w[4];
-                unsigned k[4];
-                int cnt;                              // live samples of this lane's voxel
-                unsigned rec_wr;
-                {
-                    const float mx = group_max<8>(s0.lg);
-                    const float e = __expf(s0.lg - mx);
-                    const float ssum = group_sum<8>(e);
-                    const float a = m ? e * __builtin_amdgcn_rcpf(ssum * (float)__popc(m)) : 0.0f;
-                    Bilinear s;
-                    bilinear_setup<false>(s0.u.x + s0.of.x * inv_w, s0.u.y + s0.of.y * inv_h, mh, mw, s);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        w[t] = a * s.w[t];
-                        k[t] = (unsigned)s.key[t] * RB;            // row offset inside a plane
-                    }
-                    // compaction: live samples first (in point order), all-zero records behind them
-                    const bool live = (w[0] + w[1] + w[2] + w[3]) != 0.0f;      // weights are >= 0
-                    const unsigned long long bal = __ballot(live);
-                    const unsigned gm = (unsigned)(bal >> (lane & ~7)) & 0xffu;
-                    const unsigned below = (1u << l8) - 1u;
-                    cnt = __popc(gm);
-                    const int slot = live ? __popc(gm & below) : cnt + __popc(~gm & below);
-                    rec_wr = rec_wr0 + (unsigned)slot * 8u;
-                }
-                // ---------------- phase B: two voxels per sub-iteration, lane = (voxel, corner, 4*NV channels)
-                const int nsub = min(4, p_hi - p_lo - 4 * it);
-                if (it == 1) VER_TL(6);
-                // Records travel from the phase-A lanes to the corner slots through the wave's 512-B LDS table.  Other
-                // lanes of the wave read them: LDS serves one wave's requests in order, so no wait is needed in hardware,
-                // but the compiler must know (without the fence it forwarded the previous pair's loads to the lanes that
-                // did not store -- legal for a single thread, wrong here).
-                u32x4_t recs[P / 2];
-                // the record {weight word, row offset}: the weight is fp32, or (w, w) as packed fp16 in mode 2
-                typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-                u32x2_t rec[4];
+        // per-tile WAVE-UNIFORM base pointers; a lane's address is base + 32-bit byte offset (one 24-bit multiply-add),
+        // which the memory instructions take as SGPR base + VGPR offset -- no 64-bit VALU arithmetic per access
+        const char* lg_base = reinterpret_cast<const char*>(logits + ((size_t)b * Nq * heads + h) * P);
+        const char* of_base = reinterpret_cast<const char*>(offs + ((size_t)b * Nq * heads + h) * P * 2);
+        const char* uv_base = reinterpret_cast<const char*>(uv + ((size_t)b * Ncam + c) * Nq * D * 2);
+        const uint8_t* vis_base = vis + (size_t)b * Nq;
+        char* out_base = reinterpret_cast<char*>(slots + ((size_t)b * Nq * heads + h) * HD);
+        const unsigned hp4 = (unsigned)(heads * P * 4), hhd4 = (unsigned)(heads * HD * 4), d8 = (unsigned)(D * 8);
+        auto load_sample = [&](int n) -> Sample {
+            Sample sm;
+            const unsigned nn = (unsigned)(n < 0 ? -n - 1 : n);          // < 2^24 voxels (checked by the host wrapper)
+            sm.m = (unsigned)vis_base[nn];           // raw: a dead entry's mask is cleared where the record is used
+            sm.lg = *reinterpret_cast<const float*>(lg_base + (__umul24(nn, hp4) + (unsigned)l8 * 4u));
+            sm.of = *reinterpret_cast<const float2*>(of_base + (__umul24(nn, hp4) * 2u + (unsigned)l8 * 8u));
+            sm.u = *reinterpret_cast<const float2*>(uv_base + (__umul24(nn, d8) + (unsigned)ad * 8u));
+            return sm;
+        };
+        int n0 = un0, n1 = un1, n2 = un2;
+        Sample s0 = {};
+        if (iters > 0) s0 = load_sample(n0);      // requested before the tile barrier: the latency hides behind it
+        VER_TL(1);
+        __builtin_amdgcn_s_waitcnt(0);            // this wave's share of the tile has landed
+        VER_TL(2);
+        to_f16();
+        VER_TL(3);
+        __syncthreads();                          // the tile is complete
+        __builtin_amdgcn_s_setprio(0);
+        VER_TL(4);
+        const unsigned base4 = smem_lds + lane_off;
+        __builtin_amdgcn_s_waitcnt(0x0f70);       // the first iteration's operands (requested before the tile barrier)
+        // operands: voxel ids two wave iterations ahead, sample records one ahead (all loads and stores of the loop
+        // are unconditional, so the compiler's vmcnt waits never have to drain the young output stores)
+        for (int it = 0; it < iters; ++it) {
+            const Sample s1 = load_sample(n1);
+            const int n3 = load_id(it + 3);
+            // ---------------- phase A: lane = sampling point l8 of voxel (s4, v2)
+            const unsigned m = n0 < 0 ? 0u : s0.m;
+            float w[4];
+            unsigned k[4];
+            int cnt;                              // live samples of this lane's voxel
+            unsigned rec_wr;
+            {
+                const float mx = group_max<8>(s0.lg);
+                const float e = __expf(s0.lg - mx);
+                const float ssum = group_sum<8>(e);
+                const float a = m ? e * __builtin_amdgcn_rcpf(ssum * (float)__popc(m)) : 0.0f;
+                Bilinear s;
+                bilinear_setup<false>(s0.u.x + s0.of.x * inv_w, s0.u.y + s0.of.y * inv_h, mh, mw, s);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    if constexpr (MATH == 2) {
-                        const _Float16 hw = (_Float16)w[t];
-                        rec[t].x = __builtin_bit_cast(unsigned, h2_t{hw, hw});
-                    } else {
-                        rec[t].x = __float_as_uint(w[t]);
-                    }
-                    rec[t].y = k[t];
+                    w[t] = a * s.w[t];
+                    k[t] = (unsigned)s.key[t] * RB;            // row offset inside a plane
                 }
-                if (s4 == 0) {
+                // compaction: live samples first (in point order), all-zero records behind them
+                const bool live = (w[0] + w[1] + w[2] + w[3]) != 0.0f;      // weights are >= 0
+                const unsigned long long bal = __ballot(live);
+                const unsigned gm = (unsigned)(bal >> (lane & ~7)) & 0xffu;
+                const unsigned below = (1u << l8) - 1u;
+                cnt = __popc(gm);
+                const int slot = live ? __popc(gm & below) : cnt + __popc(~gm & below);
+                rec_wr = rec_wr0 + (unsigned)slot * 8u;
+            }
+            // ---------------- phase B: two voxels per sub-iteration, lane = (voxel, corner, 4*NV channels)
+            const int nsub = min(4, p_hi - p_lo - 4 * it);
+            if (it == 1) VER_TL(6);
+            // Records travel from the phase-A lanes to the corner slots through the wave's 512-B LDS table.  Other
+            // lanes of the wave read them: LDS serves one wave's requests in order, so no wait is needed in hardware,
+            // but the compiler must know (without the fence it forwarded the previous pair's loads to the lanes that
+            // did not store -- legal for a single thread, wrong here).
+            u32x4_t recs[P / 2];
+            // the record {weight word, row offset}: the weight is fp32, or (w, w) as packed fp16 for bf16 tiles
+            typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+            u32x2_t rec[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if constexpr (F32) {
+                    rec[t].x = __float_as_uint(w[t]);
+                } else {
+                    const _Float16 hw = (_Float16)w[t];
+                    rec[t].x = __builtin_bit_cast(unsigned, h2_t{hw, hw});
+                }
+                rec[t].y = k[t];
+            }
+            if (s4 == 0) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) *lds_ptr_mut<u32x2_t>(rec_wr + (unsigned)t * 64u) = rec[t];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+            for (int pp = 0; pp < P / 2; ++pp) recs[pp] = *lds_ptr<u32x4_t>(rec_rd + (unsigned)pp * 16u);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j > 0 && j >= nsub) break;                 // wave-uniform (an iteration exists for at least one pair)
+                const bool atomic = p_lo + 4 * it + j >= s_pairs;   // wave-uniform: the pair is in the shared region
+                const int npts = max(__builtin_amdgcn_readlane(cnt, 16 * j), __builtin_amdgcn_readlane(cnt, 16 * j + 8));
+                // `recs` holds this pair's records (requested during the previous pair's epilogue).  Publish the next
+                // pair's now -- LDS serves the wave's requests in order, so the reads of this pair's records are
+                // already done -- and request them after the FMA loop, when `recs` is free again: neither the
+                // write -> read round trip through LDS nor the read latency is exposed (85 us of a 474-us launch
+                // when they were).
+                if (j + 1 < nsub && s4 == j + 1) {
 #pragma unroll
                     for (int t = 0; t < 4; ++t) *lds_ptr_mut<u32x2_t>(rec_wr + (unsigned)t * 64u) = rec[t];
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                float acc[4 * NV];                             // fp32 tiles
+                h2_t acc2[2 * NV];                             // bf16 tiles: the same 4 * NV channels as packed fp16 pairs
 #pragma unroll
-                for (int pp = 0; pp < P / 2; ++pp) recs[pp] = *lds_ptr<u32x4_t>(rec_rd + (unsigned)pp * 16u);
+                for (int i = 0; i < 4 * NV; ++i) acc[i] = 0.0f;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (j > 0 && j >= nsub) break;                 // wave-uniform (an iteration exists for at least one pair)
-#ifdef VER_ABL_NOATOMIC
-                    const bool atomic = false;
-#else
-                    const bool atomic = p_lo + 4 * it + j >= s_pairs;   // wave-uniform: the pair is in the shared region
-#endif
-#if defined(VER_ABL_MEMONLY)
-                    const int npts = min(0, max(__builtin_amdgcn_readlane(cnt, 16 * j), __builtin_amdgcn_readlane(cnt, 16 * j + 8)));
-#elif defined(VER_ABL_NOPOINTS)
-                    const int npts = min(1, max(__builtin_amdgcn_readlane(cnt, 16 * j), __builtin_amdgcn_readlane(cnt, 16 * j + 8)));
-#else
-                    const int npts = max(__builtin_amdgcn_readlane(cnt, 16 * j), __builtin_amdgcn_readlane(cnt, 16 * j + 8));
-#endif
-                    // `recs` holds this pair's records (requested during the previous pair's epilogue).  Publish the next
-                    // pair's now -- LDS serves the wave's requests in order, so the reads of this pair's records are
-                    // already done -- and request them after the FMA loop, when `recs` is free again: neither the
-                    // write -> read round trip through LDS nor the read latency is exposed (85 us of a 474-us launch
-                    // when they were).
-                    if (j + 1 < nsub && s4 == j + 1) {
+                for (int i = 0; i < 2 * NV; ++i) acc2[i] = h2_t{(_Float16)0.0f, (_Float16)0.0f};
+                // tile vectors of a point are requested one point ahead of their FMAs (explicitly: left to itself the
+                // compiler, short of registers, funnelled every read through one register pair with a full
+                // lgkmcnt(0) wait in front of each group of FMAs)
+                typedef typename std::conditional<F32, f32x4_t, u32x2_t>::type tv_t;
+                auto rec_wbits = [&](int pt) { return (pt & 1) ? recs[pt / 2].z : recs[pt / 2].x; };
+                auto rec_a = [&](int pt) { return base4 + ((pt & 1) ? recs[pt / 2].w : recs[pt / 2].y); };
+                // (volatile: an ordinary load whose only use is in the next point's block gets sunk into it)
+                auto tile_ld = [&](unsigned addr) -> tv_t {
+                    return *(const volatile __attribute__((address_space(3))) tv_t*)(uintptr_t)addr;
+                };
+                tv_t tb[2][NV];                                // two buffers by point parity: no register copies
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) *lds_ptr_mut<u32x2_t>(rec_wr + (unsigned)t * 64u) = rec[t];
+                for (int i = 0; i < NV; ++i) tb[0][i] = tile_ld(rec_a(0) + (unsigned)i * plane);
+#pragma unroll
+                for (int pt = 0; pt < P; ++pt) {
+                    if (pt >= npts) break;                     // wave-uniform: the pair has no more live samples
+                    const unsigned wbit = rec_wbits(pt);
+                    const float wb = __uint_as_float(wbit);
+                    if (pt + 1 < P) {
+#pragma unroll
+                        for (int i = 0; i < NV; ++i) tb[(pt + 1) & 1][i] = tile_ld(rec_a(pt + 1) + (unsigned)i * plane);
                     }
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    float acc[4 * NV];
-                    h2_t acc2[2 * NV];                             // mode 2: the same 4 * NV channels as packed fp16 pairs
 #pragma unroll
-                    for (int i = 0; i < 4 * NV; ++i) acc[i] = 0.0f;
+                    for (int i = 0; i < NV; ++i) {
+                        const tv_t tc = tb[pt & 1][i];
+                        if constexpr (F32) {
+                            const float v[4] = {tc.x, tc.y, tc.z, tc.w};
 #pragma unroll
-                    for (int i = 0; i < 2 * NV; ++i) acc2[i] = h2_t{(_Float16)0.0f, (_Float16)0.0f};
-                    // tile vectors of a point are requested one point ahead of their FMAs (explicitly: left to itself the
-                    // compiler, short of registers, funnelled every read through one register pair with a full
-                    // lgkmcnt(0) wait in front of each group of FMAs)
-                    typedef typename std::conditional<F32, f32x4_t, u32x2_t>::type tv_t;
-                    auto rec_wbits = [&](int pt) { return (pt & 1) ? recs[pt / 2].z : recs[pt / 2].x; };
-                    auto rec_a = [&](int pt) { return base4 + ((pt & 1) ? recs[pt / 2].w : recs[pt / 2].y); };
-                    // (volatile: an ordinary load whose only use is in the next point's block gets sunk into it)
-                    auto tile_ld = [&](unsigned addr) -> tv_t {
-                        return *(const volatile __attribute__((address_space(3))) tv_t*)(uintptr_t)addr;
-                    };
-                    tv_t tb[2][NV];                                // two buffers by point parity: no register copies
-#pragma unroll
-                    for (int i = 0; i < NV; ++i) tb[0][i] = tile_ld(rec_a(0) + (unsigned)i * plane);
-#pragma unroll
-                    for (int pt = 0; pt < P; ++pt) {
-                        if (pt >= npts) break;                     // wave-uniform: the pair has no more live samples
-                        const unsigned wbit = rec_wbits(pt);
-                        const float wb = __uint_as_float(wbit);
-                        if (pt + 1 < P) {
-#pragma unroll
-                            for (int i = 0; i < NV; ++i) tb[(pt + 1) & 1][i] = tile_ld(rec_a(pt + 1) + (unsigned)i * plane);
-                        }
-#pragma unroll
-                        for (int i = 0; i < NV; ++i) {
-                            const tv_t tc = tb[pt & 1][i];
-                            if constexpr (MATH == 2) {
-                                const h2_t w2 = __builtin_bit_cast(h2_t, wbit);
-                                acc2[2 * i] = __builtin_elementwise_fma(__builtin_bit_cast(h2_t, (unsigned)tc.x), w2, acc2[2 * i]);
-                                acc2[2 * i + 1] = __builtin_elementwise_fma(__builtin_bit_cast(h2_t, (unsigned)tc.y), w2, acc2[2 * i + 1]);
-                            } else {
-                                float v[4];
-                                if constexpr (F32) {
-                                    v[0] = tc.x; v[1] = tc.y; v[2] = tc.z; v[3] = tc.w;
-                                } else if constexpr (MATH == 1) {
-                                    const h2_t a = __builtin_bit_cast(h2_t, (unsigned)tc.x), b2 = __builtin_bit_cast(h2_t, (unsigned)tc.y);
-                                    v[0] = (float)a.x; v[1] = (float)a.y; v[2] = (float)b2.x; v[3] = (float)b2.y;
-                                } else {
-                                    v[0] = __uint_as_float(tc.x << 16); v[1] = __uint_as_float(tc.x & 0xffff0000u);
-                                    v[2] = __uint_as_float(tc.y << 16); v[3] = __uint_as_float(tc.y & 0xffff0000u);
-                                }
-#pragma unroll
-                                for (int q = 0; q < 4; ++q) acc[i * 4 + q] = __builtin_fmaf(wb, v[q], acc[i * 4 + q]);
-                            }
-                        }
-                    }
-                    if (it == 1 && j == 0) VER_TL(7);
-                    if (j + 1 < nsub) {                            // next pair's records: the latency hides behind the epilogue
-                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-                        for (int pp = 0; pp < P / 2; ++pp) recs[pp] = *lds_ptr<u32x4_t>(rec_rd + (unsigned)pp * 16u);
-                    }
-                    // fold the four corner slots: rows of 16 lanes first (transposing: even rows keep channels {0,1}
-                    // of each vector, odd rows {2,3}), then the two slots of a row
-                    float out[2 * NV];
-                    if constexpr (MATH == 2) {
-                        // the same fold on the packed pairs: (ch0, ch1) and (ch2, ch3) of a vector are one register each
-#pragma unroll
-                        for (int i = 0; i < NV; ++i) {
-                            float a = __builtin_bit_cast(float, acc2[2 * i]), b2 = __builtin_bit_cast(float, acc2[2 * i + 1]);
-                            permlane16_swap(a, b2);
-                            h2_t sum = __builtin_bit_cast(h2_t, a) + __builtin_bit_cast(h2_t, b2);
-                            sum = sum + __builtin_bit_cast(h2_t, dpp_mov<0x128>(__builtin_bit_cast(float, sum)));      // row_ror:8
-                            out[2 * i + 0] = (float)sum.x;
-                            out[2 * i + 1] = (float)sum.y;
-                        }
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < NV; ++i) {
-                            permlane16_swap(acc[i * 4 + 0], acc[i * 4 + 2]);
-                            permlane16_swap(acc[i * 4 + 1], acc[i * 4 + 3]);
-                            out[2 * i + 0] = acc[i * 4 + 0] + acc[i * 4 + 2];
-                            out[2 * i + 1] = acc[i * 4 + 1] + acc[i * 4 + 3];
-                        }
-#pragma unroll
-                        for (int i = 0; i < 2 * NV; ++i) out[i] += dpp_mov<0x128>(out[i]);      // row_ror:8
-                    }
-#ifndef VER_CS_NO_PRESTORE_WAIT
-                    // gfx950 counts loads and stores in ONE counter, and the number of stores of an iteration is not a
-                    // compile-time constant: the compiler's wait for the next iteration's operands (requested at the top of
-                    // this one) is a vmcnt(0) at the top of the next -- right behind this iteration's last store.  Waiting
-                    // HERE, in front of the iteration's first store, covers the same requests a phase A and a pair later.
-                    if (j == 0) __builtin_amdgcn_s_waitcnt(0x0f70);       // vmcnt(0) only
-#endif
-                    const int na = __builtin_amdgcn_readlane(n0, 16 * j), nb = __builtin_amdgcn_readlane(n0, 16 * j + 8);
-                    const int n = half ? nb : na;
-                    const unsigned rowoff = __umul24((unsigned)(n < 0 ? -n - 1 : n), hhd4) + (unsigned)(l8 * 4 + rho * 2) * 4u;
-                    float* live_row = reinterpret_cast<float*>(out_base + rowoff);
-                    // the only dead voxel of the plain-store region is the pad entry of an odd single count: last pair
-                    const bool has_pad = !atomic && (s_n & 1) && p_lo + 4 * it + j == s_pairs - 1;     // wave-uniform
-#ifdef VER_ABL_NOSTORE
-                    if (out[0] == 12345.678f)
-#endif
-                    if (!atomic) {
-                        // both slots of a row hold the sums and share the stores
-                        float* row = live_row;
-#ifdef VER_ABL_DUMMYOUT
-                        row = g_sca_dummy_row + (blockIdx.x & 255) * 256 + l8 * 4 + rho * 2;      // timing: no HBM write stream
-#else
-                        if (has_pad && n < 0) row = g_sca_dummy_row + (blockIdx.x & 255) * 256 + l8 * 4 + rho * 2;
-#endif
-#pragma unroll
-                        for (int kk = 0; kk < (NV + 1) / 2; ++kk) {
-                            float o2[2];
-                            float* dst;
-                            if (2 * kk + 1 < NV) {
-                                float a0 = out[4 * kk], a1 = out[4 * kk + 1], b0 = out[4 * kk + 2], b1 = out[4 * kk + 3];
-                                asm("" : "+v"(b0), "+v"(b1));      // (keeps the selects out of scratch memory)
-                                o2[0] = sigma ? b0 : a0;
-                                o2[1] = sigma ? b1 : a1;
-                                dst = row + (2 * kk + sigma) * 32;
-                            } else {
-                                // odd plane count: both slots of a row hold the last vector's two sums -- each writes ONE
-                                // of them (4-byte stores, 32 lanes = one 128-byte line) instead of both writing both
-                                float a0 = out[4 * kk], a1 = out[4 * kk + 1];
-                                asm("" : "+v"(a1));
-                                const float one = sigma ? a1 : a0;
-                                __builtin_nontemporal_store(one, row + 2 * kk * 32 + sigma);
-                                continue;
-                            }
-                            store_vec<2, true>(dst, o2);
-                        }
-                    } else {
-                        float* row = live_row;                     // dead voxel (odd tail): adds zeros to a live shared row
-#pragma unroll
-                        for (int i = 0; i < NV; ++i) {
-                            float a0 = out[2 * i], b0 = out[2 * i + 1];
-                            asm("" : "+v"(b0));
-                            const float val = n < 0 ? 0.0f : (sigma ? b0 : a0);
-                            atomicAdd(row + i * 32 + sigma, val);
+                            for (int q = 0; q < 4; ++q) acc[i * 4 + q] = __builtin_fmaf(wb, v[q], acc[i * 4 + q]);
+                        } else {
+                            const h2_t w2 = __builtin_bit_cast(h2_t, wbit);
+                            acc2[2 * i] = __builtin_elementwise_fma(__builtin_bit_cast(h2_t, (unsigned)tc.x), w2, acc2[2 * i]);
+                            acc2[2 * i + 1] = __builtin_elementwise_fma(__builtin_bit_cast(h2_t, (unsigned)tc.y), w2, acc2[2 * i + 1]);
                         }
                     }
                 }
-                n0 = n1; n1 = n2; n2 = n3;
-                s0 = s1;
-                VER_TL(8 + it);
+                if (it == 1 && j == 0) VER_TL(7);
+                if (j + 1 < nsub) {                            // next pair's records: the latency hides behind the epilogue
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+                    for (int pp = 0; pp < P / 2; ++pp) recs[pp] = *lds_ptr<u32x4_t>(rec_rd + (unsigned)pp * 16u);
+                }
+                // fold the four corner slots: rows of 16 lanes first (transposing: even rows keep channels {0,1}
+                // of each vector, odd rows {2,3}), then the two slots of a row
+                float out[2 * NV];
+                if constexpr (F32) {
+#pragma unroll
+                    for (int i = 0; i < NV; ++i) {
+                        permlane16_swap(acc[i * 4 + 0], acc[i * 4 + 2]);
+                        permlane16_swap(acc[i * 4 + 1], acc[i * 4 + 3]);
+                        out[2 * i + 0] = acc[i * 4 + 0] + acc[i * 4 + 2];
+                        out[2 * i + 1] = acc[i * 4 + 1] + acc[i * 4 + 3];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 2 * NV; ++i) out[i] += dpp_mov<0x128>(out[i]);      // row_ror:8
+                } else {
+                    // the same fold on the packed pairs: (ch0, ch1) and (ch2, ch3) of a vector are one register each
+#pragma unroll
+                    for (int i = 0; i < NV; ++i) {
+                        float a = __builtin_bit_cast(float, acc2[2 * i]), b2 = __builtin_bit_cast(float, acc2[2 * i + 1]);
+                        permlane16_swap(a, b2);
+                        h2_t sum = __builtin_bit_cast(h2_t, a) + __builtin_bit_cast(h2_t, b2);
+                        sum = sum + __builtin_bit_cast(h2_t, dpp_mov<0x128>(__builtin_bit_cast(float, sum)));      // row_ror:8
+                        out[2 * i + 0] = (float)sum.x;
+                        out[2 * i + 1] = (float)sum.y;
+                    }
+                }
+                // gfx950 counts loads and stores in ONE counter, and the number of stores of an iteration is not a
+                // compile-time constant: the compiler's wait for the next iteration's operands (requested at the top of
+                // this one) is a vmcnt(0) at the top of the next -- right behind this iteration's last store.  Waiting
+                // HERE, in front of the iteration's first store, covers the same requests a phase A and a pair later.
+                if (j == 0) __builtin_amdgcn_s_waitcnt(0x0f70);       // vmcnt(0) only
+                const int na = __builtin_amdgcn_readlane(n0, 16 * j), nb = __builtin_amdgcn_readlane(n0, 16 * j + 8);
+                const int n = half ? nb : na;
+                const unsigned rowoff = __umul24((unsigned)(n < 0 ? -n - 1 : n), hhd4) + (unsigned)(l8 * 4 + rho * 2) * 4u;
+                float* live_row = reinterpret_cast<float*>(out_base + rowoff);
+                // the only dead voxel of the plain-store region is the pad entry of an odd single count: last pair
+                const bool has_pad = !atomic && (s_n & 1) && p_lo + 4 * it + j == s_pairs - 1;     // wave-uniform
+                if (!atomic) {
+                    // both slots of a row hold the sums and share the stores
+                    float* row = live_row;
+                    if (has_pad && n < 0) row = g_sca_dummy_row + (blockIdx.x & 255) * 256 + l8 * 4 + rho * 2;
+#pragma unroll
+                    for (int kk = 0; kk < (NV + 1) / 2; ++kk) {
+                        float o2[2];
+                        float* dst;
+                        if (2 * kk + 1 < NV) {
+                            float a0 = out[4 * kk], a1 = out[4 * kk + 1], b0 = out[4 * kk + 2], b1 = out[4 * kk + 3];
+                            asm("" : "+v"(b0), "+v"(b1));      // (keeps the selects out of scratch memory)
+                            o2[0] = sigma ? b0 : a0;
+                            o2[1] = sigma ? b1 : a1;
+                            dst = row + (2 * kk + sigma) * 32;
+                        } else {
+                            // odd plane count: both slots of a row hold the last vector's two sums -- each writes ONE
+                            // of them (4-byte stores, 32 lanes = one 128-byte line) instead of both writing both
+                            float a0 = out[4 * kk], a1 = out[4 * kk + 1];
+                            asm("" : "+v"(a1));
+                            const float one = sigma ? a1 : a0;
+                            __builtin_nontemporal_store(one, row + 2 * kk * 32 + sigma);
+                            continue;
+                        }
+                        store_vec<2, true>(dst, o2);
+                    }
+                } else {
+                    float* row = live_row;                     // dead voxel (odd tail): adds zeros to a live shared row
+#pragma unroll
+                    for (int i = 0; i < NV; ++i) {
+                        float a0 = out[2 * i], b0 = out[2 * i + 1];
+                        asm("" : "+v"(b0));
+                        const float val = n < 0 ? 0.0f : (sigma ? b0 : a0);
+                        atomicAdd(row + i * 32 + sigma, val);
+                    }
+                }
             }
-            VER_TL(5);
+            n0 = n1; n1 = n2; n2 = n3;
+            s0 = s1;
+            VER_TL(8 + it);
         }
+        VER_TL(5);
     }
 }
 
@@ -1361,8 +1238,8 @@ __global__ __launch_bounds__(512) void k_sca_bwd(const VT* __restrict__ value, c
 // ------------------------------------------------------------------------------------------
 // Backward, split in two atomic-free (in LDS) kernels for head_dim >= 32 (16-lane groups):
 //
-//  k_sca_bwd_off  d(offsets), d(logits): the forward kernel's structure (double-buffered LDS-DMA
-//     tiles over heads, phase A / phase B, DPP broadcast).  Phase B forms the per-corner dots
+//  k_sca_bwd_off  d(offsets), d(logits): the forward kernel's structure (LDS-DMA tiles over
+//     heads, phase A / phase B, DPP broadcast).  Phase B forms the per-corner dots
 //     <g, V[row]> (16-lane DPP butterflies); the phase-A lane that owns the corner picks its dot
 //     up and combines it with its own bilinear weight / slope; softmax backward is a second
 //     butterfly over the row.  Rows of voxels seen by one camera are plain stores, others fp32
@@ -1384,7 +1261,7 @@ __global__ __launch_bounds__(kFwdThreads) void k_sca_bwd_off(
     const VT* __restrict__ value, const float* __restrict__ offs, const float* __restrict__ logits,
     const float* __restrict__ uv, const uint8_t* __restrict__ vis, const int* __restrict__ vis_list,
     const int* __restrict__ vis_cnt, const float* __restrict__ gslots, float* goffs, float* glogits, int Ncam,
-    int Nq, int D, int heads, int mh, int mw, int nchunks, int chunk, int hsplit, int nbuf) {
+    int Nq, int D, int heads, int mh, int mw, int nchunks, int chunk, int hsplit) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int CPL = HD / 16;
     constexpr int LPP = 16 / P, CPN = 4 / LPP;
@@ -1392,8 +1269,7 @@ __global__ __launch_bounds__(kFwdThreads) void k_sca_bwd_off(
     const int STEP = nwaves_rt * 4;
     using M16 = ChMap<HD, 16>;
     const int Nk = mh * mw;
-    const size_t tile_elems = (size_t)Nk * HD;
-    VT* tiles = reinterpret_cast<VT*>(smem);
+    VT* tile = reinterpret_cast<VT*>(smem);           // one buffer (512 threads, two workgroups per CU overlap each other)
     int bid = blockIdx.x;
     const int ck = bid % nchunks;
     bid /= nchunks;
@@ -1416,20 +1292,12 @@ __global__ __launch_bounds__(kFwdThreads) void k_sca_bwd_off(
     const float inv_w = 1.0f / (float)mw, inv_h = 1.0f / (float)mh;
     constexpr unsigned kRowBytes = HD * sizeof(VT);
 
-    if (nbuf == 2) stage_tile<HD, VT>(tiles, vown + (size_t)h0 * HD, rstride, Nk, wave, nwaves_rt);
     for (int hh = 0; hh < heads_per; ++hh) {
         const int h = h0 + hh;
-        const int cur = nbuf == 2 ? (hh & 1) : 0;
-        VT* tile = tiles + cur * tile_elems;
-        if (nbuf == 1) {
-            __syncthreads();
-            stage_tile<HD, VT>(tile, vown + (size_t)h * HD, rstride, Nk, wave, nwaves_rt);
-        }
+        __syncthreads();                              // everyone is done with the previous head
+        stage_tile<HD, VT>(tile, vown + (size_t)h * HD, rstride, Nk, wave, nwaves_rt);
         __builtin_amdgcn_s_waitcnt(0);
         __syncthreads();
-        if (nbuf == 2 && hh + 1 < heads_per)
-            stage_tile<HD, VT>(tiles + (cur ^ 1) * tile_elems, vown + (size_t)(h + 1) * HD, rstride, Nk, wave,
-                               nwaves_rt);
         const unsigned char* tile0 = reinterpret_cast<const unsigned char*>(tile + M16::off0(lr));
         const unsigned char* tile1 = reinterpret_cast<const unsigned char*>(tile + M16::off1(lr));
 
@@ -1717,12 +1585,9 @@ __global__ __launch_bounds__(kValThreads) void k_sca_bwd_val(
 typedef __bf16 mm_bf16x8 __attribute__((ext_vector_type(8)));
 typedef short mm_s16x4 __attribute__((ext_vector_type(4)));
 typedef short mm_s16x8 __attribute__((ext_vector_type(8)));
-#ifndef VER_MM_WAVES
-#define VER_MM_WAVES 4
-#endif
 // waves per workgroup of k_sca_bwd_mm.  4 (two workgroups per CU, 246 VGPRs) measured 591 us per 192-viewpoint launch;
 // 8 (one workgroup per CU at 179 VGPRs) 771 us; 8 squeezed into 128 VGPRs for two workgroups per CU spills: 1759 us.
-constexpr int kMmWaves = VER_MM_WAVES;
+constexpr int kMmWaves = 4;
 constexpr int kMmDss = 36;            // floats per row of the D / S^T buffer [tile row][32 voxels + pad]: rows 4 banks apart
 
 __device__ __forceinline__ void mm_split(const float (&f)[8], mm_bf16x8& hi, mm_bf16x8& lo) {
@@ -1745,7 +1610,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_sca_bwd_mm(
     const uint16_t* __restrict__ value, const float* __restrict__ offs, const float* __restrict__ logits,
     const float* __restrict__ uv, const uint8_t* __restrict__ vis, const int* __restrict__ fwd_list,
     const int* __restrict__ fwd_cnt, const GST* __restrict__ gslots, GVT* __restrict__ gvalue, float* goffs,
-    float* glogits, int Ncam, int Nq, int D, int heads, int mh, int mw, int total_wgs, int head_major_views, int reverse) {
+    float* glogits, int Ncam, int Nq, int D, int heads, int mh, int mw, int total_wgs, int head_major_views) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int P = 8, NT = HD / 16, KS = HD / 32, MI = 16 / NW;
     static_assert(HD % 32 == 0, "k-steps of 32 channels");
@@ -1763,8 +1628,8 @@ __global__ __launch_bounds__(NW * 64, 2) void k_sca_bwd_mm(
     int bid = (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
     if (bid >= total_wgs) return;
     // last viewpoint first: the grad rows (531 MB at 192 viewpoints) were written just before this launch in ascending row
-    // order through the 256-MB memory-side cache -- the end of the tensor is what is still resident (k_sca_fwd_cs: `reverse`)
-    if (reverse) bid = total_wgs - 1 - bid;
+    // order through the 256-MB memory-side cache -- the end of the tensor is what is still resident (as in k_sca_fwd_cs)
+    bid = total_wgs - 1 - bid;
     const int h = bid % heads;
     bid /= heads;
     const int c = bid % Ncam, b = bid / Ncam;
@@ -2059,14 +1924,32 @@ __global__ __launch_bounds__(NW * 64, 2) void k_sca_bwd_mm(
 // ------------------------------------------------------------------------------------------
 namespace {
 
-int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 constexpr int kFwdChunk = 2048;
 constexpr int kBwdChunk = 4096;
 constexpr size_t kMaxLds = 160 * 1024;
+
+// Dynamic LDS of k_sca_bwd_mm (tile + D / S^T buffer + grad rows hi, lo) for this head_dim and map, or 0 when the
+// matrix-core backward does not fit.  The ONE place that decides it: the dtype / layout queries of the ABI and the
+// launcher can never disagree.
+size_t sca_bwd_mm_lds(int head_dim, int map_h, int map_w) {
+    if (head_dim % 32 != 0 || head_dim > 128) return 0;
+    const int nk = map_h * map_w, mt = (nk + 15) / 16;
+    const size_t tile_b = ((size_t)nk * head_dim * 2 + 15) & ~(size_t)15, ds_b = (size_t)nk * kMmDss * 4,
+                 g_b = (size_t)2 * 32 * head_dim * 2;
+    // the last tile-row tile reads (16 mt - nk) rows past the tile / past DS: they must stay inside the allocation
+    const bool slack_ok = (size_t)(16 * mt - nk) * head_dim * 2 <= ds_b && (size_t)(16 * mt - nk) * kMmDss * 4 <= g_b;
+    return (mt <= 16 && slack_ok && tile_b + ds_b + g_b <= kMaxLds) ? tile_b + ds_b + g_b : 0;
+}
+
+// set the kernel's dynamic-LDS limit, launch it, check the launch
+template <typename K, typename... Args>
+int launch_lds(const char* what, K kern, unsigned blocks, int threads, size_t lds, hipStream_t st, Args... args) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "%s: LDS attribute: %s", what, hipGetErrorString(e));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, st, args...);
+    return ver_check_launch(what);
+}
 
 template <typename F>
 int dispatch_shape(int hd, int points, F&& f) {
@@ -2149,19 +2032,12 @@ extern "C" int ver_hits_from_mask(const uint8_t* bev_mask, int B, int Ncam, int 
     return ver_check_launch("ver_hits_from_mask/k_build_lists");
 }
 
-static bool sca_bwd_use_mm() {       // read ONCE per process: the dtype query and the dispatch can never disagree
-    static const int v = env_int("VER_SCA_BWD_MM", 1);
-    return v != 0;
-}
-
 // value layouts ver_sca_forward / ver_sca_backward read: the reference's [B, Ncam, Nk, heads, HD] always; head-major
 // [heads, B, Ncam, Nk, HD] (VER_SCA_VALUE_HEAD_MAJOR) where the fast kernels are built for it
 extern "C" int ver_sca_head_major_supported(int value_dtype, int head_dim, int points, int map_h, int map_w) {
-    static const int use_cs = env_int("VER_SCA_FWD_CS", 1);
-    static const int cs_math = env_int("VER_SCA_FWD_MATH", 2);
-    static const int cs_nload = env_int("VER_SCA_CS_NLOAD", 0);
-    return (value_dtype == VER_BF16 && points == 8 && map_h == 14 && map_w == 14 && use_cs && cs_math == 2 && cs_nload == 0 &&
-            (head_dim == 32 || head_dim == 64 || head_dim == 96 || head_dim == 128) && sca_bwd_use_mm()) ? 1 : 0;
+    return (value_dtype == VER_BF16 && points == 8 && map_h == 14 && map_w == 14 &&
+            (head_dim == 32 || head_dim == 64 || head_dim == 96 || head_dim == 128) &&
+            sca_bwd_mm_lds(head_dim, map_h, map_w) > 0) ? 1 : 0;
 }
 
 // The zero fill of ver_sca_forward as a call of its own: it depends on the hit table only, so a caller can run it on a
@@ -2201,31 +2077,18 @@ extern "C" int ver_sca_forward(const void* value, int value_dtype, const float* 
     // two ways to overlap the tile stream with the gather: one 16-wave workgroup per CU with a
     // double-buffered tile, or two 8-wave workgroups per CU with one tile each (finer work split:
     // 32 instead of 64 voxel slots per pass over a camera's ~140 visible voxels)
-    static const int fwd_threads = [] {
-        const char* e = getenv("VER_SCA_FWD_THREADS");
-        const int t = e ? atoi(e) : 512;               // measured: 512 beats 1024 by 5-15 % (B = 32..256)
-        return (t == 256 || t == 512 || t == 1024) ? t : 512;
-    }();
-    // double-buffer the tile inside the workgroup when the CU's LDS holds it for every resident
-    // workgroup (one of 16 waves, or two of 8 waves: bf16 tiles of 14x14x96 fit four times)
-    static const int force_nbuf = [] {
-        const char* e = getenv("VER_SCA_FWD_NBUF");
-        return e ? atoi(e) : 0;
-    }();
-    const size_t wgs_per_cu = kFwdThreads / fwd_threads;
-    int nbuf = 2 * wgs_per_cu * tile_bytes <= kMaxLds ? 2 : 1;
-    if (force_nbuf == 1 || (force_nbuf == 2 && 2 * tile_bytes <= kMaxLds)) nbuf = force_nbuf;
+    constexpr int kGenThreads = 512;                   // measured: 512 beats 1024 by 5-15 % (B = 32..256)
+    // double-buffer the tile inside the workgroup when the CU's LDS holds it for both resident
+    // workgroups (bf16 tiles of 14x14x96 fit four times)
+    const int nbuf = 2 * (kFwdThreads / kGenThreads) * tile_bytes <= kMaxLds ? 2 : 1;
     const size_t lds = tile_bytes * nbuf;
     const int nchunks = (Nq + kFwdChunk - 1) / kFwdChunk;
     // heads are walked inside a workgroup (the tile stream is double buffered); split them over
     // several workgroups only while the grid would not yet fill the 256 CUs a few times over
-    static const long min_wgs = [] {
-        const char* e = getenv("VER_SCA_FWD_MIN_WGS");
-        return e ? atol(e) : 6144L;                    // heads split until >= 12 workgroups per residency slot
+    constexpr long kGenMinWgs = 6144;                  // heads split until >= 12 workgroups per residency slot
                                                        // (2 per CU): 2-5 % over 1536 at B = 64..256
-    }();
     int hsplit = 1;
-    while (hsplit < heads && heads % (hsplit * 2) == 0 && (long)B * Ncam * hsplit * nchunks < min_wgs) hsplit *= 2;
+    while (hsplit < heads && heads % (hsplit * 2) == 0 && (long)B * Ncam * hsplit * nchunks < kGenMinWgs) hsplit *= 2;
     hipStream_t st = (hipStream_t)stream;
     VER_REQUIRE((flags & ~(VER_SCA_ROWS_PREZEROED | VER_SCA_VALUE_HEAD_MAJOR)) == 0, VER_EINVAL,
                 "ver_sca_forward: unknown flags 0x%x", flags);
@@ -2241,40 +2104,21 @@ extern "C" int ver_sca_forward(const void* value, int value_dtype, const float* 
     return dispatch_shape(head_dim, points, [&](auto hd, auto g, auto pp) {
         constexpr int HD = decltype(hd)::value, G = decltype(g)::value, P = decltype(pp)::value;
         auto launch = [&](auto kern, auto vptr) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess)
-                return ver_fail(VER_ELAUNCH, "ver_sca_forward: LDS attribute: %s", hipGetErrorString(e));
-            const unsigned blocks = (unsigned)B * Ncam * hsplit * nchunks;
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(fwd_threads), lds, st, vptr, offsets, logits, uv, vis, vis_list,
-                               vis_cnt, slots, Ncam, Nq, D, heads, map_h, map_w, nchunks, kFwdChunk, hsplit, nbuf);
-            return ver_check_launch("ver_sca_forward");
+            return launch_lds("ver_sca_forward", kern, (unsigned)B * Ncam * hsplit * nchunks, kGenThreads, lds, st, vptr,
+                              offsets, logits, uv, vis, vis_list, vis_cnt, slots, Ncam, Nq, D, heads, map_h, map_w, nchunks,
+                              kFwdChunk, hsplit, nbuf);
         };
         if constexpr (P == 8 && HD % 32 == 0) {
-            // corner-slot kernel (fp32 and bf16 tiles); VER_SCA_FWD_CS=0 falls back to the generic 16-lane kernel.
-            // Launch shape = measured optima at the vocc size (scratch/r02/sweep_*.sh); the environment variables
-            // exist for scratch/bench_gather.py sweeps:
-            //   threads   256 (bf16 tiles: four single-tile workgroups per CU) / 512 (fp32 tiles: two per CU)
-            //   nload     0: every wave stages its share of the tile, one buffer; > 0: that many loader waves stream
-            //             tiles through two buffers for a workgroup that walks many tiles (measured slower here: one
-            //             16-wave workgroup per CU cannot hold more waves than four small ones, and its tiles split
-            //             into 4-5 pairs per wave with a second, nearly empty phase-A pass)
-            //   hsplit    heads are split over this many units (8: one head per unit)
-            //   units/wg  1: one unit per workgroup (0: as many as it takes to fill the CUs `wgs_per_cu` times)
-            static const int use_cs = env_int("VER_SCA_FWD_CS", 1);
+            // corner-slot kernel (fp32 and bf16 tiles).  Launch shape = measured optima at the vocc size
+            // (docs/HISTORY.md section 3.1):
+            //   threads   256 (bf16 tiles: four single-tile workgroups per CU) / 512 (fp32 tiles: two per CU);
+            //             320 / 384 lose
+            //   hsplit    heads are split over up to 8 units (8 heads: one head per unit), one unit per workgroup
             const bool f32 = value_dtype == VER_F32;
-            static const int cs_threads_f32 = env_int("VER_SCA_CS_THREADS_F32", 512);
-            static const int cs_threads_bf16 = env_int("VER_SCA_CS_THREADS_BF16", 256);
-            static const int cs_nload = env_int("VER_SCA_CS_NLOAD", 0);
-            static const int cs_hsplit = env_int("VER_SCA_CS_HSPLIT", 8);
-            static const int cs_upw = env_int("VER_SCA_CS_UNITS_PER_WG", 1);
-            static const int cs_wgs_per_cu = env_int("VER_SCA_CS_WGS_PER_CU", 1);
-            static const int cs_reverse = env_int("VER_SCA_CS_REVERSE", 1);
-            int pt = f32 ? cs_threads_f32 : cs_threads_bf16;
-            if (pt % 64 != 0 || pt < 128 || pt > 1024) pt = f32 ? 512 : 256;
-            const int nlp = (cs_nload >= 0 && cs_nload < pt / 64) ? cs_nload : 0;
+            const int pt = f32 ? 512 : 256;
+            constexpr int kCsHsplit = 8;
             const size_t tb = (tile_bytes + 15) & ~(size_t)15;
-            const size_t ldsp = (nlp > 0 ? 2 : 1) * tb + (size_t)(pt / 64) * 512;
+            const size_t ldsp = tb + (size_t)(pt / 64) * 512;        // tile + one 512-B record table per wave
             // k_sca_fwd_cs addresses slots / offsets / logits / uv with 32-bit byte offsets (`__umul24` row products):
             // every one of them must stay below 2^32 and the 24-bit multiplicands below 2^24, else the generic
             // kernel (64-bit addressing) takes the launch
@@ -2285,48 +2129,27 @@ extern "C" int ver_sca_forward(const void* value, int value_dtype, const float* 
                                     (size_t)heads * points * 8 < ((size_t)1 << 24) && Nq < (1 << 24) &&
                                     // unit indices go through 32-bit magic divisions (cs_div): exact below 2^32 / divisor
                                     (size_t)B * Ncam * nchunks * heads < ((size_t)1 << 24);
-            if (use_cs && ldsp <= kMaxLds && cs_addr_ok) {
+            if (ldsp <= kMaxLds && cs_addr_ok) {
                 int hsp = 1;
-                while (hsp < cs_hsplit && hsp < heads && heads % (hsp * 2) == 0) hsp *= 2;
+                while (hsp < kCsHsplit && hsp < heads && heads % (hsp * 2) == 0) hsp *= 2;
                 const int units = B * Ncam * nchunks * hsp;
-                int upw = cs_upw;
-                if (upw <= 0) {
-                    int dev = 0, cus = 256;
-                    if (hipGetDevice(&dev) == hipSuccess)
-                        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                    if (cus <= 0) cus = 256;
-                    const int slots_wg = cus * (cs_wgs_per_cu > 0 ? cs_wgs_per_cu : 1);
-                    upw = (units + slots_wg - 1) / slots_wg;
-                }
-                const int grid = ((units + upw - 1) / upw + 7) & ~7;     // multiple of 8: dealt to the XCDs in blocks
-                const CsMagic mg = {cs_magic(hsp), cs_magic(nchunks), cs_magic(Ncam), cs_magic(heads / hsp),
-                                    cs_magic(pt / 64 - nlp)};
+                const unsigned grid = (unsigned)((units + 7) & ~7);      // multiple of 8: dealt to the XCDs in blocks
+                const CsMagic mg = {cs_magic(hsp), cs_magic(nchunks), cs_magic(Ncam), cs_magic(pt / 64)};
                 auto launch_cs = [&](auto kern, auto vptr) {
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);
-                    if (e != hipSuccess)
-                        return ver_fail(VER_ELAUNCH, "ver_sca_forward: LDS attribute: %s", hipGetErrorString(e));
-                    hipLaunchKernelGGL(kern, dim3(grid), dim3(pt), ldsp, st, vptr, offsets, logits, uv, vis, fwd_list,
-                                       fwd_cnt, slots, Ncam, Nq, D, heads, map_h, map_w, nchunks, kFwdChunk, hsp, units, upw,
-                                       nlp, head_major ? B : 0, cs_reverse, heads / hsp, mg);
-                    return ver_check_launch("ver_sca_forward");
+                    return launch_lds("ver_sca_forward", kern, grid, pt, ldsp, st, vptr, offsets, logits, uv, vis, fwd_list,
+                                      fwd_cnt, slots, Ncam, Nq, D, heads, map_h, map_w, nchunks, kFwdChunk, hsp, units,
+                                      head_major ? B : 0, heads / hsp, mg);
                 };
                 const bool k196 = map_h * map_w == 196;                // plane offsets become immediates
                 if (f32) {
                     if (k196) return launch_cs(k_sca_fwd_cs<HD, float, 196>, (const float*)value);
                     return launch_cs(k_sca_fwd_cs<HD, float, 0>, (const float*)value);
                 }
-                // VER_SCA_FWD_MATH: 0 bf16 tile + fp32 unpack and accumulation (exact), 2 fp16 tile + packed fp16
-                // accumulation over a voxel's points (default: DESIGN.md section 3.1)
-                static const int cs_math = env_int("VER_SCA_FWD_MATH", 2);
-                static const int cs_one = env_int("VER_SCA_CS_ONE", 1);          // 0: the general form for every launch shape
-                const bool one = cs_one && nlp == 0 && upw == 1 && hsp == heads && nchunks == 1;
-                if (head_major && one) return launch_cs(k_sca_fwd_cs<HD, uint16_t, 196, 2, true, true>, (const uint16_t*)value);
-                if (head_major) return launch_cs(k_sca_fwd_cs<HD, uint16_t, 196, 2, true>, (const uint16_t*)value);
-                if (k196 && cs_math == 2 && one) return launch_cs(k_sca_fwd_cs<HD, uint16_t, 196, 2, false, true>, (const uint16_t*)value);
-                if (k196 && cs_math == 2) return launch_cs(k_sca_fwd_cs<HD, uint16_t, 196, 2>, (const uint16_t*)value);
+                const bool one = hsp == heads && nchunks == 1;         // one tile per workgroup: the compile-time form
+                if (head_major && one) return launch_cs(k_sca_fwd_cs<HD, uint16_t, 196, true, true>, (const uint16_t*)value);
+                if (head_major) return launch_cs(k_sca_fwd_cs<HD, uint16_t, 196, true>, (const uint16_t*)value);
+                if (k196 && one) return launch_cs(k_sca_fwd_cs<HD, uint16_t, 196, false, true>, (const uint16_t*)value);
                 if (k196) return launch_cs(k_sca_fwd_cs<HD, uint16_t, 196>, (const uint16_t*)value);
-                if (cs_math == 2) return launch_cs(k_sca_fwd_cs<HD, uint16_t, 0, 2>, (const uint16_t*)value);
                 return launch_cs(k_sca_fwd_cs<HD, uint16_t, 0>, (const uint16_t*)value);
             }
         }
@@ -2342,13 +2165,8 @@ extern "C" int ver_sca_forward(const void* value, int value_dtype, const float* 
 // dtype ver_sca_backward writes d(value) in most cheaply for this problem: VER_BF16 on the matrix-core path (bf16 value
 // tiles, 8 points, head_dim % 32 == 0, tile fits), else VER_F32.  VER_F32 is always accepted.
 extern "C" int ver_sca_backward_grad_dtype(int value_dtype, int head_dim, int points, int map_h, int map_w) {
-    if (value_dtype != VER_BF16 || points != 8 || head_dim % 32 != 0 || head_dim > 128) return VER_F32;
-    if (!sca_bwd_use_mm()) return VER_F32;
-    const int nk = map_h * map_w, mt = (nk + 15) / 16;
-    const size_t tile_b = ((size_t)nk * head_dim * 2 + 15) & ~(size_t)15, ds_b = (size_t)nk * kMmDss * 4,
-                 g_b = (size_t)2 * 32 * head_dim * 2;
-    const bool slack_ok = (size_t)(16 * mt - nk) * head_dim * 2 <= ds_b && (size_t)(16 * mt - nk) * kMmDss * 4 <= g_b;
-    return (mt <= 16 && slack_ok && tile_b + ds_b + g_b <= kMaxLds) ? VER_BF16 : VER_F32;
+    if (value_dtype != VER_BF16 || points != 8) return VER_F32;
+    return sca_bwd_mm_lds(head_dim, map_h, map_w) > 0 ? VER_BF16 : VER_F32;
 }
 
 extern "C" int ver_sca_backward(const void* value, int value_dtype, const float* offsets, const float* logits,
@@ -2391,28 +2209,18 @@ extern "C" int ver_sca_backward(const void* value, int value_dtype, const float*
     return dispatch_shape(head_dim, points, [&](auto hd, auto g, auto pp) {
         constexpr int HD = decltype(hd)::value, G = decltype(g)::value, P = decltype(pp)::value;
         if constexpr (P == 8 && HD % 32 == 0) {
-            // bf16 value tiles: everything on the matrix cores, one kernel (VER_SCA_BWD_MM=0: the two-kernel path below)
-            const bool use_mm = sca_bwd_use_mm();
-            static const int bwd_reverse = env_int("VER_SCA_BWD_REVERSE", 1);
-            const int nk = map_h * map_w, mt = (nk + 15) / 16;
-            const size_t tile_b = ((size_t)nk * HD * 2 + 15) & ~(size_t)15, ds_b = (size_t)nk * kMmDss * 4, g_b = (size_t)2 * 32 * HD * 2;
-            // the last tile-row tile reads (16 mt - nk) rows past the tile / past DS: they must stay inside the allocation
-            const bool slack_ok = (size_t)(16 * mt - nk) * HD * 2 <= ds_b && (size_t)(16 * mt - nk) * kMmDss * 4 <= g_b;
-            if (use_mm && value_dtype == VER_BF16 && mt <= 16 && slack_ok && tile_b + ds_b + g_b <= kMaxLds) {
-                const size_t lds_mm = tile_b + ds_b + g_b;
+            // bf16 value tiles: everything on the matrix cores, one kernel, whenever it fits (it beats the two-kernel path below)
+            const size_t lds_mm = sca_bwd_mm_lds(HD, map_h, map_w);
+            if (value_dtype == VER_BF16 && lds_mm > 0) {
+                const int nk = map_h * map_w;
                 auto launch_mm = [&](auto kern, auto gptr, auto sptr) {
-                    hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mm);
-                    if (e2 != hipSuccess)
-                        return ver_fail(VER_ELAUNCH, "ver_sca_backward: LDS attribute: %s", hipGetErrorString(e2));
                     typedef std::remove_pointer_t<decltype(gptr)> gv_t;
                     typedef std::remove_cv_t<std::remove_pointer_t<decltype(sptr)>> gs_t;
                     const int wgs = B * Ncam * heads;
-                    hipLaunchKernelGGL(kern, dim3((unsigned)((wgs + 7) & ~7)), dim3(kMmWaves * 64), lds_mm, st, (const uint16_t*)value,
-                                       offsets, logits, uv, vis, fwd_list, fwd_cnt, (const gs_t*)(const void*)grad_slots,
-                                       (gv_t*)grad_value, grad_offsets, grad_logits, Ncam, Nq, D, heads, map_h, map_w, wgs,
-                                       head_major ? B : 0, bwd_reverse);
-                    return ver_check_launch("ver_sca_backward/k_sca_bwd_mm");
+                    return launch_lds("ver_sca_backward/k_sca_bwd_mm", kern, (unsigned)((wgs + 7) & ~7), kMmWaves * 64, lds_mm, st,
+                                      (const uint16_t*)value, offsets, logits, uv, vis, fwd_list, fwd_cnt,
+                                      (const gs_t*)(const void*)grad_slots, (gv_t*)grad_value, grad_offsets, grad_logits, Ncam, Nq,
+                                      D, heads, map_h, map_w, wgs, head_major ? B : 0);
                 };
                 if (grad_bf16) {
                     VER_REQUIRE(grad_value_dtype == VER_BF16, VER_EUNSUPPORTED, "ver_sca_backward: bf16 grad_slots go with bf16 grad_value");
@@ -2432,32 +2240,18 @@ extern "C" int ver_sca_backward(const void* value, int value_dtype, const float*
                     "ver_sca_backward: bf16 d(value) is only written by the matrix-core kernel; this shape runs the fp32 paths");
         if constexpr (G == 16) {
             if (map_h * map_w <= kValMaxRows) {
-                // ---- d(offsets), d(logits): forward-shaped kernel
-                const size_t tile_bytes = (size_t)map_h * map_w * head_dim * esz;
-                static const int off_threads = [] {
-                    const char* ev = getenv("VER_SCA_BWD_THREADS");
-                    const int t = ev ? atoi(ev) : 512;
-                    return (t == 256 || t == 512 || t == 1024) ? t : 512;
-                }();
-                static const long off_min_wgs = [] {
-                    const char* ev = getenv("VER_SCA_BWD_MIN_WGS");
-                    return ev ? atol(ev) : 12288L;      // one head per workgroup up to B*Ncam = 1536: 4-7 % faster than 768
-                }();
-                const int nbuf = (off_threads == kFwdThreads && 2 * tile_bytes <= kMaxLds) ? 2 : 1;
-                const size_t lds_off = tile_bytes * nbuf;
+                // ---- d(offsets), d(logits): forward-shaped kernel, 512 threads (two workgroups per CU, one tile each)
+                const size_t lds_off = (size_t)map_h * map_w * head_dim * esz;
+                constexpr int kOffThreads = 512;
+                constexpr long kOffMinWgs = 12288;      // one head per workgroup up to B*Ncam = 1536: 4-7 % faster than 768
                 const int nch = (Nq + kFwdChunk - 1) / kFwdChunk;
                 int hsplit = 1;
-                while (hsplit < heads && heads % (hsplit * 2) == 0 && (long)B * Ncam * hsplit * nch < off_min_wgs)
+                while (hsplit < heads && heads % (hsplit * 2) == 0 && (long)B * Ncam * hsplit * nch < kOffMinWgs)
                     hsplit *= 2;
                 auto launch_off = [&](auto kern, auto vptr) {
-                    hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_off);
-                    if (e2 != hipSuccess)
-                        return ver_fail(VER_ELAUNCH, "ver_sca_backward: LDS attribute: %s", hipGetErrorString(e2));
-                    hipLaunchKernelGGL(kern, dim3((unsigned)B * Ncam * hsplit * nch), dim3(off_threads), lds_off, st, vptr,
-                                       offsets, logits, uv, vis, vis_list, vis_cnt, grad_slots, grad_offsets,
-                                       grad_logits, Ncam, Nq, D, heads, map_h, map_w, nch, kFwdChunk, hsplit, nbuf);
-                    return ver_check_launch("ver_sca_backward/k_sca_bwd_off");
+                    return launch_lds("ver_sca_backward/k_sca_bwd_off", kern, (unsigned)B * Ncam * hsplit * nch, kOffThreads,
+                                      lds_off, st, vptr, offsets, logits, uv, vis, vis_list, vis_cnt, grad_slots, grad_offsets,
+                                      grad_logits, Ncam, Nq, D, heads, map_h, map_w, nch, kFwdChunk, hsplit);
                 };
                 int r2;
                 if (value_dtype == VER_BF16) {
@@ -2470,30 +2264,18 @@ extern "C" int ver_sca_backward(const void* value, int value_dtype, const float*
                 // ---- d(value): event sort, no value tile
                 const size_t lds_val = (size_t)kValSub * HD * 4 + (size_t)kValSub * P * 4 * (4 + 2 + 2) +
                                        3 * kValMaxRows * sizeof(int);
-                auto kv = k_sca_bwd_val<HD, P>;
-                hipError_t e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(kv),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_val);
-                if (e3 != hipSuccess)
-                    return ver_fail(VER_ELAUNCH, "ver_sca_backward: LDS attribute: %s", hipGetErrorString(e3));
-                hipLaunchKernelGGL(kv, dim3((unsigned)B * Ncam * heads * nchunks), dim3(kValThreads), lds_val, st, offsets,
-                                   logits, uv, vis, vis_list, vis_cnt, grad_slots, grad_value_f32, Ncam, Nq, D, heads,
-                                   map_h, map_w, nchunks, kBwdChunk);
-                return ver_check_launch("ver_sca_backward/k_sca_bwd_val");
+                return launch_lds("ver_sca_backward/k_sca_bwd_val", k_sca_bwd_val<HD, P>, (unsigned)B * Ncam * heads * nchunks,
+                                  kValThreads, lds_val, st, offsets, logits, uv, vis, vis_list, vis_cnt, grad_slots,
+                                  grad_value_f32, Ncam, Nq, D, heads, map_h, map_w, nchunks, kBwdChunk);
             }
         }
         // narrow heads / large maps: single-kernel LDS-atomic path
         VER_REQUIRE(lds <= kMaxLds, VER_EUNSUPPORTED, "ver_sca_backward: %dx%dx%d tiles (%zu B) exceed LDS", map_h,
                     map_w, head_dim, lds);
         auto launch = [&](auto kern, auto vptr) {
-            hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e2 != hipSuccess)
-                return ver_fail(VER_ELAUNCH, "ver_sca_backward: LDS attribute: %s", hipGetErrorString(e2));
-            const unsigned blocks = (unsigned)B * Ncam * heads * nchunks;
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds, st, vptr, offsets, logits, uv, vis, vis_list, vis_cnt,
-                               grad_slots, grad_value_f32, grad_offsets, grad_logits, Ncam, Nq, D, heads, map_h, map_w,
-                               nchunks, kBwdChunk);
-            return ver_check_launch("ver_sca_backward");
+            return launch_lds("ver_sca_backward", kern, (unsigned)B * Ncam * heads * nchunks, 512, lds, st, vptr, offsets, logits,
+                              uv, vis, vis_list, vis_cnt, grad_slots, grad_value_f32, grad_offsets, grad_logits, Ncam, Nq, D,
+                              heads, map_h, map_w, nchunks, kBwdChunk);
         };
         if constexpr (HD % 8 == 0) {
             if (value_dtype == VER_BF16) return launch(k_sca_bwd<HD, G, P, uint16_t>, (const uint16_t*)value);

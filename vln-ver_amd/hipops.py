@@ -259,7 +259,7 @@ def hits_from_mask(reference_points_cam, bev_mask):
 
 
 _SIDE_STREAMS = {}
-SCA_PREZERO = os.environ.get('VER_SCA_PREZERO', '1') != '0'
+SCA_PREZERO = True       # False (assign from a script): the gather zero-fills in line instead of on a side stream
 
 
 def _side_stream(device):
@@ -282,7 +282,7 @@ def sca_prepare_slots(hit, row_floats):
     (``ver_sca_zero_rows``).  The fill depends on the hit table only, so a caller that does this before the
     projections feeding the gather (value_proj, sampling_offsets / attention_weights) hides it under them instead
     of paying it in front of the gather.  Returns None when it cannot be overlapped safely (stream capture,
-    VER_SCA_PREZERO=0): ``sca_gather`` then fills in line, as before."""
+    ``SCA_PREZERO`` False): ``sca_gather`` then fills in line, as before."""
     if not SCA_PREZERO or torch.cuda.is_current_stream_capturing():
         return None
     dev = hit.vis.device

@@ -15,7 +15,6 @@ restructured for the GPU:
   viewpoint carries its own hit lists, so results per viewpoint equal a bs=1 reference run.
 """
 import math
-import os
 import warnings
 
 import torch
@@ -27,11 +26,11 @@ from ..registry import ATTENTION, build_attention
 from .bricks import BaseModule, PendingResidual, const_tensor, constant_init, lowp_view, tall_linear, xavier_init
 
 
-# VER_SCA_HEAD_MAJOR=1: value_proj writes the head-major layout (contiguous gather tiles).  OFF by default: measured at 192
+# True: value_proj writes the head-major layout (contiguous gather tiles); a script may assign it.  OFF: measured at 192
 # viewpoints per launch the gather gains 14 us forward + 6 us backward per layer, but the batched N = 96 GEMM that produces
 # the layout costs 1.07 ms against 0.31 ms for the plain [rows, 768] GEMM (a permuting copy after the plain GEMM: + 0.19 ms)
 # -- the step as a whole is faster with the reference's layout.
-_HEAD_MAJOR = os.environ.get('VER_SCA_HEAD_MAJOR', '0') == '1'
+_HEAD_MAJOR = False
 
 
 @ATTENTION.register_module(force=True)
