@@ -110,6 +110,13 @@ class GraphedLiftStep:
     device, so the captured update uses the right bias corrections on every replay (``optimizer.replayed()`` keeps the host's
     counts in step, ``optimizer.refresh()`` uploads a learning rate a scheduler has moved).
 
+    Eager steps of the same optimizer may run between the calls (the ragged last batch of an epoch), with either
+    ``zero_grad`` mode: every replay rewrites the optimizer's device pointer table to this capture's gradient buffers, so
+    ``replayed()`` drops the host's record of that table and the next eager step uploads its own pointers again.  The graph
+    reads the optimizer's device buffers by raw address: ``optimizer.load_state_dict``, unpickling, or an eager step over
+    another set of tensors (a parameter whose first gradient arrives after the capture) replaces them and makes this object
+    unusable -- ``refresh()`` raises at the top of the next call, before the replay; build a new GraphedLiftStep then.
+
     ``model(feats, w2p, org, gt) -> scalar loss`` (bench.py's LiftTrainer); ``optimizer``: a ClipAdamW over the model's trainable
     parameters.  Construction runs ``warmup`` REAL eager steps on the sample inputs (allocator, AdamW state, library
     heuristics) before the capture -- they train the model like any other step.  One rank only: the gradient all-reduce of

@@ -17,6 +17,19 @@ hyper-parameters and the per-tensor update counts, which the kernel advances its
 every call: a changed gradient / moment / parameter pointer (``zero_grad(set_to_none=True)``, ``load_state_dict``,
 ``model.to()``), a changed lr (schedulers) or a step count that was set from outside is uploaded again before the launch --
 nothing is cached by object identity.
+
+Two rules tie that host record to captured graphs (tests/test_optim_graph_gpu.py):
+
+* The record of the pointer table holds only while the last writer of the table was an EAGER step.  A captured ``step()``
+  turns its table copy into a graph node, so every replay rewrites the device table to the capture's own gradient buffers
+  behind the host's back: the capture and ``replayed()`` forget the record, and the next eager step uploads its pointers
+  again even when its gradients sit where they sat before the replay.  Any number of graphs may share one optimizer: each
+  replay restores its own table.
+* A graph reads the table / hyper-parameter / count buffers (and the chunk tables) by raw address.  They are kept referenced
+  for as long as the optimizer lives, and whatever replaces or drops them once a ``step()`` has been captured --
+  ``load_state_dict``, ``__setstate__``, an eager step over another set of tensors (a parameter whose first gradient
+  arrives after the capture) -- makes every earlier capture INVALID: ``refresh()`` and ``replayed()``, which a replay passes
+  through (``graphs.GraphedLiftStep.__call__``), raise until ``prepare_capture()`` and a new capture.
 """
 
 import numpy as np
@@ -32,7 +45,9 @@ class ClipAdamW(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, max_norm=max_norm))
         self._tables = {}
         self._dev = None             # what the device buffers hold: dict(ptrs, hyper, steps, n) + the buffers themselves
-        self._keep = []              # pinned staging buffers a captured graph copies from on every replay
+        self._keep = []              # what captured graphs read by raw address: pinned staging buffers, device tables
+        self._captured = None        # per-parameter states of the captured step(), while that capture may be replayed
+        self._stale = None           # why the earlier captures may not be replayed any more
 
     # ------------------------------------------------------------------ host-side bookkeeping
     def _chunk_tables(self, sizes, device):
@@ -96,6 +111,8 @@ class ClipAdamW(torch.optim.Optimizer):
             if capturing:
                 raise RuntimeError('ClipAdamW: the first step() for this set of parameters inside a graph capture; run '
                                    '`prepare_capture()` (or one eager step) before capturing')
+            if d is not None:
+                self._invalidate('an eager step() over %d tensors replaced the device buffers of %d' % (n, d['n']))
             d = self._dev = dict(n=n, device=dev, ptrs=None, hyper=None, steps=None,
                                  table=torch.empty(4 * n, dtype=torch.int64, device=dev),
                                  hyper_dev=torch.empty(n, 6, dtype=torch.float32, device=dev),
@@ -112,9 +129,10 @@ class ClipAdamW(torch.optim.Optimizer):
             if capturing:
                 self._keep.append(src)
             dst.copy_(src.view(dst.shape), non_blocking=True)
-        if d['ptrs'] != ptrs:
+        if capturing or d['ptrs'] != ptrs:
             push(d['table'], np.asarray(ptrs, dtype=np.int64))
-            d['ptrs'] = ptrs
+            # (a captured copy has not run, and every replay runs it without the host: no record of it)
+            d['ptrs'] = None if capturing else ptrs
         if d['hyper'] != hyper or d['steps'] != steps:
             if capturing:
                 raise RuntimeError('ClipAdamW: hyper-parameters / step counts changed inside a graph capture; call '
@@ -145,9 +163,12 @@ class ClipAdamW(torch.optim.Optimizer):
         ptrs = ([p.data_ptr() for p in ps] + [g.data_ptr() for g in gs] + [st['exp_avg'].data_ptr() for st in states]
                 + [st['exp_avg_sq'].data_ptr() for st in states])
         steps = [st['step'] for st in states]
+        if not capturing and self._captured and [id(st) for st in states] != [id(st) for st in self._captured]:
+            self._invalidate('an eager step() ran over other tensors than the captured one')
         d = self._upload(ptrs, hyper, steps, dev, capturing)
         norm = torch.zeros((), dtype=torch.float32, device=dev)
-        sizes, chunk_tensor, chunk_index, partial = self._chunk_tables([p.numel() for p in ps], dev)
+        tables = self._chunk_tables([p.numel() for p in ps], dev)
+        sizes, chunk_tensor, chunk_index, partial = tables
         L = hipops.lib()
         hipops._launch('ver_clip_adamw_step', lambda: L.ver_clip_adamw_step_tensors(
             hipops._p(d['table']), hipops._p(sizes), hipops._p(chunk_tensor), hipops._p(chunk_index), hipops._p(d['hyper_dev']),
@@ -155,7 +176,8 @@ class ClipAdamW(torch.optim.Optimizer):
             hipops._stream()))
         if capturing:
             # nothing has run: the replays advance the device counts, ``replayed()`` the host's
-            self._captured = states
+            self._captured, self._stale = states, None
+            self._keep.append((d['table'], d['hyper_dev'], d['steps_dev'], tables))
         else:
             for st in states:
                 st['step'] += 1
@@ -175,24 +197,37 @@ class ClipAdamW(torch.optim.Optimizer):
             raise RuntimeError('ClipAdamW.prepare_capture(): run one eager step over the parameters of the step first')
         self._stage = torch.empty(4 * n, dtype=torch.int64).pin_memory()
 
-    def replayed(self, times=1):
-        """A graph holding ``step()`` was replayed ``times`` times: advance the host's step counts to what the device holds."""
-        states = getattr(self, '_captured', None)
+    def _invalidate(self, why):
+        """The buffers the captured graphs read are being replaced or dropped (they stay referenced in ``_keep``, so a replay
+        that slips past the guard still reads memory of its own): no replay until a new capture."""
+        if self.__dict__.get('_captured'):
+            self._captured, self._stale = None, why
+
+    def _live_capture(self, who):
+        states = self.__dict__.get('_captured')
         if not states:
-            raise RuntimeError('ClipAdamW.replayed(): no step() has been captured')
+            raise RuntimeError('ClipAdamW.%s(): no captured step() may be replayed (%s); a new capture is needed -- one eager '
+                               'step, `prepare_capture()`, then capture `step()` again'
+                               % (who, self.__dict__.get('_stale') or 'none has been captured'))
+        return states
+
+    def replayed(self, times=1):
+        """A graph holding ``step()`` was replayed ``times`` times: advance the host's step counts to what the device holds,
+        and forget the record of the pointer table -- the replay has rewritten it to the capture's gradient buffers."""
+        states = self._live_capture('replayed')
         for st in states:
             st['step'] += times
-        if self._dev is not None and self._dev['steps'] is not None:
-            self._dev['steps'] = [s + times for s in self._dev['steps']]
+        d = self._dev
+        d['ptrs'] = None
+        if d['steps'] is not None:
+            d['steps'] = [s + times for s in d['steps']]
 
     @torch.no_grad()
     def refresh(self):
         """Between replays: upload hyper-parameters that changed (a scheduler moved lr) into the buffers the graph reads."""
+        states = self._live_capture('refresh')
         d = self._dev
-        if d is None:
-            return
         hyper = []
-        states = getattr(self, '_captured', None) or []
         ids = {id(st) for st in states}
         for group in self.param_groups:
             b1, b2 = group['betas']
@@ -211,10 +246,14 @@ class ClipAdamW(torch.optim.Optimizer):
         for group in self.param_groups:
             for k, v in self.defaults.items():
                 group.setdefault(k, v)
+        self._invalidate('load_state_dict() replaced the state the capture was made with')
         self._dev = None             # (pointers and counts are compared on every step anyway; drop the buffers with the old state)
 
     def __setstate__(self, state):
         super().__setstate__(state)
         self.__dict__.setdefault('_tables', {})
-        self.__dict__['_dev'] = None
         self.__dict__.setdefault('_keep', [])
+        self.__dict__.setdefault('_captured', None)
+        self.__dict__.setdefault('_stale', None)
+        self._invalidate('__setstate__() replaced the state the capture was made with')
+        self.__dict__['_dev'] = None
