@@ -186,7 +186,10 @@ int ver_hits_from_mask(const uint8_t* bev_mask, int B, int Ncam, int Nq, int D,
 #define VER_SCA_VALUE_HEAD_MAJOR 2
 /*        VER_SCA_GRAD_SLOTS_BF16 (ver_sca_backward): `grad_slots` is bf16 [B, Nq, heads*head_dim] -- what the GEMM behind the
  *   gather hands back under bf16 autocast -- and is used as it is, one bf16 term per element (the fp32 form is split into
- *   bf16 hi + lo); only where ver_sca_backward_grad_dtype(...) == VER_BF16, with grad_value_dtype = VER_BF16.
+ *   bf16 hi + lo), whatever the camera count: the division by the count is done in fp32, on the sampling weight, so the three
+ *   gradients equal bit for bit those of the fp32 form on the same rows wherever no voxel is seen by more than two cameras
+ *   (with more, grad_offsets / grad_logits depend on the order of the atomic adds either way, as the slots do); only where
+ *   ver_sca_backward_grad_dtype(...) == VER_BF16, with grad_value_dtype = VER_BF16.
  */
 #define VER_SCA_GRAD_SLOTS_BF16 4
 int ver_sca_head_major_supported(int value_dtype, int head_dim, int points, int map_h, int map_w);

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import cases
+from sca_modes_helper import random_sca_case as _random_sca_case
 from util import close, golden, maxdiff, oracle, oracle_slots, pkg
 
 pytestmark = pytest.mark.gpu
@@ -182,22 +183,6 @@ def test_hits_from_reference_layout_mask():
 
 
 # ------------------------------------------------------------------------------- a4 + a5 + a6: fused gather
-def _random_sca_case(seed, B, grid, heads, hd, P, map_hw=(14, 14), D=1):
-    syn = pkg('synthetic')
-    hip = pkg('hipops')
-    rng = np.random.default_rng(seed)
-    z, h, w = grid
-    nq = z * h * w
-    nk = map_hw[0] * map_hw[1]
-    w2p, org = syn.camera_batch(B, seed=1)
-    hit = hip.project_points(T(w2p).to(DEV), T(org).to(DEV), cases.PC_RANGE, z, h, w)
-    value = rng.standard_normal((B, 6, nk, heads, hd)).astype(np.float32)
-    offsets = (rng.standard_normal((B, nq, heads, P, 2)) * 3.0).astype(np.float32)
-    logits = rng.standard_normal((B, nq, heads, P)).astype(np.float32)
-    gslots = rng.standard_normal((B, nq, heads * hd)).astype(np.float32)
-    return hit, value, offsets, logits, gslots
-
-
 @pytest.mark.parametrize('heads,hd,P,grid,mhw', [
     (8, 96, 8, (4, 15, 15), (14, 14)), (4, 8, 8, (2, 6, 5), (14, 14)), (2, 16, 4, (2, 6, 5), (14, 14)),
     (2, 32, 8, (3, 7, 7), (14, 14)), (2, 64, 4, (2, 9, 8), (14, 14)), (1, 128, 8, (2, 6, 5), (9, 11))])
@@ -348,10 +333,12 @@ def test_sca_gather_head_major_value_equals_reference_layout():
     assert rel_l2(got[3], lin.bias.grad.float().cpu()) < 5e-3
 
 
-def test_sca_backward_grad_value_dtype_contract():
+@pytest.mark.parametrize('mhw', [(14, 14), (9, 11)], ids=['14x14', '9x11'])
+def test_sca_backward_grad_value_dtype_contract(mhw):
     """C ABI: ver_sca_backward_grad_dtype names the cheapest d(value) dtype (bf16 on the matrix-core path), and
     VER_F32 is accepted for the same problem: both buffers hold the same gradient up to bf16 rounding, and the
-    d(offsets) / d(logits) of the two calls are bitwise equal."""
+    d(offsets) / d(logits) of the two calls are bitwise equal.  14x14: the kernels specialised for the 196-row tile;
+    9x11: the run-time map size (k_sca_bwd_mm<HD, 0, ...>, whose fp32-d(value) variant only this call reaches)."""
     hip = pkg('hipops')
     lib = hip.lib()
     heads, hd, P = 8, 96, 8
@@ -359,7 +346,8 @@ def test_sca_backward_grad_value_dtype_contract():
     assert lib.ver_sca_backward_grad_dtype(0, hd, P, 14, 14) == 0          # fp32 tiles
     assert lib.ver_sca_backward_grad_dtype(1, hd, 4, 14, 14) == 0          # 4 points
     assert lib.ver_sca_backward_grad_dtype(1, 8, P, 14, 14) == 0           # head_dim 8
-    hit, value, offsets, logits, gslots = _random_sca_case(23, 2, (4, 15, 15), heads, hd, P)
+    assert lib.ver_sca_backward_grad_dtype(1, hd, P, mhw[0], mhw[1]) == 1
+    hit, value, offsets, logits, gslots = _random_sca_case(23, 2, (4, 15, 15), heads, hd, P, map_hw=mhw)
     vb = T(value).to(DEV).to(torch.bfloat16)
     of, lg, gs = T(offsets).to(DEV), T(logits).to(DEV), T(gslots).to(DEV)
     B, ncam = vb.shape[0], vb.shape[1]
@@ -370,7 +358,7 @@ def test_sca_backward_grad_value_dtype_contract():
         go, gl = torch.empty_like(of), torch.empty_like(lg)
         rc = lib.ver_sca_backward(p(vb), 1, p(of), p(lg), p(hit.uv), p(hit.vis), p(hit.vis_list), p(hit.vis_cnt),
                                   p(hit.fwd_list), p(hit.fwd_cnt), p(gs), p(gv), gdt, p(go), p(gl), B, ncam, hit.Nq,
-                                  hit.D, heads, hd, P, 14, 14, 0, hip._stream())
+                                  hit.D, heads, hd, P, mhw[0], mhw[1], 0, hip._stream())
         assert rc == 0, lib.ver_last_error()
         torch.cuda.synchronize()
         assert bool(torch.isfinite(gv.float()).all())

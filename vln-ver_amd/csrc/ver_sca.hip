@@ -1603,7 +1603,7 @@ __device__ __forceinline__ void mm_split(const float (&f)[8], mm_bf16x8& hi, mm_
 // (256 threads = 32 voxels x 8 points), all NW share the matrix phases, the zero fill and the tile staging.
 // GST: dtype of grad_slots.  float: the rows are split into bf16 hi + lo (16 mantissa bits).  uint16_t (bf16, what the
 // output_proj GEMM hands back under bf16 autocast -- VER_SCA_GRAD_SLOTS_BF16): the rows are used as they are, ONE bf16 term
-// (exact except for the 1/3, 1/5, ... camera-count factors of voxels seen by 3+ cameras, which round to bf16): half the bytes
+// (exact for every camera count: the 1 / count factor rides on the sample's fp32 weight, not on the row): half the bytes
 // of the largest operand, no lo fragments, a third fewer MFMAs.
 template <int HD, int NKT, typename GVT, int NW, typename GST = float>
 __global__ __launch_bounds__(NW * 64, 2) void k_sca_bwd_mm(
@@ -1715,26 +1715,26 @@ __global__ __launch_bounds__(NW * 64, 2) void k_sca_bwd_mm(
         if (scalar) {
             uint16_t* gh = Gh + vloc * HD + p * SEG;
             uint16_t* gl = Gl + vloc * HD + p * SEG;
+            // (the grad row goes into the matrix operands AS GIVEN: the 1 / camera-count factor is applied in fp32 to the
+            //  sample's softmax weight below, which scales its dots and its events alike.  Scaling the row instead cost a bf16
+            //  row one more rounding per element wherever the count is 3, 5, 6 or 7.  A dead lane holds the row of the live
+            //  voxel it is clamped to: its dots are never stored and its events are zero)
 #pragma unroll
             for (int i = 0; i < SEG / 4; ++i) {
-                __bf16 hi[4], lo[4];
-                float gf[4];
                 if constexpr (GBF) {
-                    const uint2 t2 = ops.graw[i];
-                    gf[0] = __uint_as_float(t2.x << 16); gf[1] = __uint_as_float(t2.x & 0xffff0000u);
-                    gf[2] = __uint_as_float(t2.y << 16); gf[3] = __uint_as_float(t2.y & 0xffff0000u);
+                    *reinterpret_cast<uint2*>(gh + 4 * i) = ops.graw[i];
                 } else {
                     const float4 t4 = ops.graw[i];
-                    gf[0] = t4.x; gf[1] = t4.y; gf[2] = t4.z; gf[3] = t4.w;
-                }
+                    const float gf[4] = {t4.x, t4.y, t4.z, t4.w};
+                    __bf16 hi[4], lo[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float gs = gf[j] * icnt;
-                    hi[j] = (__bf16)gs;
-                    lo[j] = (__bf16)(gs - (float)hi[j]);
+                    for (int j = 0; j < 4; ++j) {
+                        hi[j] = (__bf16)gf[j];
+                        lo[j] = (__bf16)(gf[j] - (float)hi[j]);
+                    }
+                    *reinterpret_cast<uint2*>(gh + 4 * i) = *reinterpret_cast<const uint2*>(hi);
+                    *reinterpret_cast<uint2*>(gl + 4 * i) = *reinterpret_cast<const uint2*>(lo);
                 }
-                *reinterpret_cast<uint2*>(gh + 4 * i) = *reinterpret_cast<const uint2*>(hi);
-                if constexpr (!GBF) *reinterpret_cast<uint2*>(gl + 4 * i) = *reinterpret_cast<const uint2*>(lo);
             }
         }
         // next chunk's operands and the id after that: in flight during the rest of this chunk
@@ -1805,6 +1805,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_sca_bwd_mm(
             const float mx = group_max<8>(lg);
             const float ex = __expf(lg - mx);
             const float a = ex / group_sum<8>(ex);
+            const float ai = a * icnt;                 // (the camera average: the dots and the events are of the unscaled row)
             Bilinear s;
             bilinear_setup<true>(u.x + of.x * inv_w, u.y + of.y * inv_h, mh, mw, s);
             float sa = 0.0f, sx = 0.0f, sy = 0.0f;
@@ -1814,11 +1815,11 @@ __global__ __launch_bounds__(NW * 64, 2) void k_sca_bwd_mm(
                 sa += s.w[t] * dot;
                 sx += s.gx[t] * dot;
                 sy += s.gy[t] * dot;
-                coef[t] = live ? a * s.w[t] : 0.0f;
+                coef[t] = live ? ai * s.w[t] : 0.0f;
                 key[t] = s.key[t];
             }
             const float dsum = group_sum<8>(a * sa);
-            const float gx = a * sx, gy = a * sy, gl = a * (sa - dsum);         // d x_pix / d offset = 1
+            const float gx = ai * sx, gy = ai * sy, gl = ai * (sa - dsum);      // d x_pix / d offset = 1
             if (live) {
                 float* go = goffs + (qh * P + p) * 2;
                 float* gw = glogits + qh * P + p;
