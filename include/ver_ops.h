@@ -899,6 +899,48 @@ int ver_dattn3d_backward(const void* value, int value_dtype, const int64_t* shap
                          int out_dtype, void* grad_value, void* grad_offsets, void* grad_logits, float* grad_ref,
                          int B, int num_keys, int heads, int head_dim, int levels, int points, int Nq, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Decoder self-attention between the input projections and out_proj (additive to ABI 31; csrc/ver_mha.hip): what
+ * torch.nn.MultiheadAttention (the mmcv MultiheadAttention wrapper of vocc.py's DetrTransformerDecoderLayer, called with
+ * need_weights=True) runs between its in-projection Linears and out_proj -- head transposes, q scaling, bmm, softmax,
+ * dropout, bmm, transpose back -- without the head-averaged weights nobody reads.  No masks.
+ *   q            f32 | bf16 [Nq, B, heads*head_dim]   row pitch ldq: ELEMENTS between consecutive (n, b) rows, so q and k
+ *   k, v         as q       [Nk, B, heads*head_dim]   (pitches ldk, ldv) may be column halves of one [N, B, 2C] GEMM output
+ *   seed         i64 device [1]                       may be NULL when p_drop == 0
+ *   out          as q       [Nq, B, heads*head_dim]   dense, written in full
+ *   lse          f32        [B, heads, Nq]            the row's max + log(sum exp), saved for the backward
+ * All arithmetic outside the matrix products is fp32:
+ *   S[i,j]  = (q_i . k_j) / sqrt(head_dim)            the scale on the fp32 product, not on a rounded q
+ *   P       = softmax_j(S), the row maximum subtracted
+ *   Pd[i,j] = keep(idx, seed) ? P[i,j] / (1 - p_drop) : 0,   idx = ((b*heads + h)*Nq + i)*Nk + j;  keep, thresh and scale
+ *             are ver_add_ln_forward's (the murmur finaliser, thresh = (uint32_t)((1.0f - p_drop) * 16777216.0f))
+ *   out[i,b,h,:] = sum_j Pd[i,j] * v[j,b,h,:]
+ * bf16 operands: the products run on v_mfma_f32_16x16x32_bf16 with fp32 accumulators; P / Pd and dS are rounded to bf16
+ * (RNE) only as MFMA operands; ragged sizes are padded in LDS.  fp32 operands: fp32 VALU products.
+ * ver_mha_backward takes the same operands plus grad_out (dense, operand dtype), lse, seed and p_drop, recomputes S and P
+ * from q, k and lse with the same keep decisions, and WRITES IN FULL grad_q, grad_k, grad_v (operand dtype, pitches ldgq,
+ * ldgk, ldgv: grad_q and grad_k may be the halves of one [N, B, 2C] buffer):
+ *   dV = Pd^T dO;  dPd = dO V^T;  dP = keep ? dPd / (1 - p) : 0;  dS = P * (dP - sum_j(dP * P));
+ *   dQ = dS K / sqrt(hd);  dK = dS^T Q / sqrt(hd)
+ * One workgroup owns a whole (b, head): no float atomics, no workspace, nothing for the caller to zero; every gradient
+ * element is written exactly once in a fixed summation order -- the same inputs give the same bits on every run, and a
+ * sample's result does not depend on B or on its place in the batch (apart from idx under dropout).
+ * One launch forward, one backward; no memset node, no allocation, no host read: both calls can be captured.
+ * B == 0 or Nq == 0: VER_OK, nothing is launched and no pointer is looked at.  Nk == 0 with Nq > 0, another null pointer, a
+ * dtype other than 0 (f32) / 1 (bf16), or a q / k / v / grad_out that is not 16-byte aligned: VER_EINVAL.
+ * Supported (VER_EUNSUPPORTED beyond, the message names the limit; ver_mha_supported answers 1 / 0 for a shape, for both
+ * dtypes and both directions, without touching the device): 1 <= Nq, Nk <= 128; head_dim a multiple of 8 up to 128; every
+ * pitch a multiple of 8 and at least heads*head_dim; B*heads < 2^31; 0 <= p_drop < 1.
+ */
+int ver_mha_supported(int B, int heads, int head_dim, int Nq, int Nk);
+int ver_mha_forward(const void* q, const void* k, const void* v, int dtype, long ldq, long ldk, long ldv,
+                    const int64_t* seed, float p_drop, void* out, float* lse, int B, int heads, int head_dim, int Nq, int Nk,
+                    void* stream);
+int ver_mha_backward(const void* q, const void* k, const void* v, int dtype, long ldq, long ldk, long ldv,
+                     const void* grad_out, const float* lse, const int64_t* seed, float p_drop, void* grad_q, void* grad_k,
+                     void* grad_v, long ldgq, long ldgk, long ldgv, int B, int heads, int head_dim, int Nq, int Nk,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,16 +22,7 @@ __device__ __forceinline__ uint32_t f2bf(float f) {   // round to nearest even
     return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 
-// keep decision of element `idx` (murmur3 finaliser of idx ^ seed, 24 bits against the threshold)
-__device__ __forceinline__ bool keep_elem(uint64_t idx, uint64_t seed, uint32_t thresh) {
-    uint64_t h = idx * 0x9E3779B97F4A7C15ull + seed;
-    h ^= h >> 33;
-    h *= 0xff51afd7ed558ccdull;
-    h ^= h >> 33;
-    h *= 0xc4ceb9fe1a85ec53ull;
-    h ^= h >> 33;
-    return (uint32_t)(h & 0xffffffu) < thresh;
-}
+// (the keep decision of element `idx`, keep_elem, is in ver_common.h: ver_mha.hip takes the same one)
 
 template <bool ABF16>
 __device__ __forceinline__ void load_a4(const void* a, long off, float (&v)[4]) {

@@ -150,3 +150,16 @@ __device__ __forceinline__ float group_max(float v) {
 }
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
+
+// Dropout keep decision of element `idx` under `seed` (ver_addln.hip, ver_mha.hip): the murmur3 finaliser of
+// idx * golden + seed, its low 24 bits against thresh = (uint32_t)((1.0f - p_drop) * 16777216.0f).  No mask tensor: the
+// backward pass recomputes the decision.  hipops.dropout_keep_host is the same rule in numpy.
+__device__ __forceinline__ bool keep_elem(uint64_t idx, uint64_t seed, uint32_t thresh) {
+    uint64_t h = idx * 0x9E3779B97F4A7C15ull + seed;
+    h ^= h >> 33;
+    h *= 0xff51afd7ed558ccdull;
+    h ^= h >> 33;
+    h *= 0xc4ceb9fe1a85ec53ull;
+    h ^= h >> 33;
+    return (uint32_t)(h & 0xffffffu) < thresh;
+}

@@ -1314,6 +1314,125 @@ def voxel_deform_attn(value, spatial_shapes, level_start_index, reference_points
 
 
 # ------------------------------------------------------------------------------------------
+def mha_supported(B, heads, head_dim, Nq, Nk):
+    """Whether ver_mha_* take the shape (the range is stated in include/ver_ops.h); no device call."""
+    return bool(lib().ver_mha_supported(B, heads, head_dim, Nq, Nk))
+
+
+def dropout_keep_host(indices, seed, p_drop):
+    """The kernels' dropout keep rule (csrc/ver_common.h keep_elem) in numpy: bool array, True where the element with flat
+    index ``indices`` is kept under ``seed``.  uint64 wrap-around arithmetic; the threshold is computed in float32, as the
+    kernels compute it."""
+    import numpy as np
+    idx = np.asarray(indices).astype(np.uint64)
+    with np.errstate(over='ignore'):
+        h = idx * np.uint64(0x9E3779B97F4A7C15) + np.uint64(int(seed) & (2 ** 64 - 1))
+        h ^= h >> np.uint64(33)
+        h *= np.uint64(0xff51afd7ed558ccd)
+        h ^= h >> np.uint64(33)
+        h *= np.uint64(0xc4ceb9fe1a85ec53)
+        h ^= h >> np.uint64(33)
+    thresh = np.uint64(int((np.float32(1.0) - np.float32(p_drop)) * np.float32(16777216.0)))
+    return (h & np.uint64(0xffffff)) < thresh
+
+
+def _row_pitch(t):
+    """(t or a contiguous copy of it, elements between consecutive rows of its flattened leading dimensions): a [N, B, C]
+    view with last-dimension stride 1 and a uniform row pitch (a column slice of a wider GEMM output) goes as it is."""
+    _, b, c = t.shape
+    ld = t.stride(0) if b == 1 else t.stride(1)
+    if (t.stride(2) == 1 and (b == 1 or t.stride(0) == b * ld) and ld >= c and ld % 8 == 0
+            and t.data_ptr() % 16 == 0):
+        return t, ld
+    return t.contiguous(), c
+
+
+def _mha_operand(t, name):
+    """A GPU tensor in fp32 or bf16 (anything else is widened to fp32); unlike ``_gpu`` it leaves a strided view alone."""
+    if not t.is_cuda:
+        raise RuntimeError('%s must be a GPU tensor: the VER ops only exist as HIP kernels' % name)
+    return t if t.dtype in (torch.float32, torch.bfloat16) else t.float()
+
+
+class MultiheadAttentionCoreFunction(Function):
+    """Softmax attention between the input projections and out_proj (ver_mha_forward / _backward): q [Nq, B, C], k, v
+    [Nk, B, C] in the layout the Linears leave them in -> [Nq, B, C].  One launch each way; the backward recomputes the
+    probabilities and the dropout decisions from q, k, the saved row log-sum-exp and the seed.  ``k`` None: ``q`` is the
+    [N, B, 2C] output of ONE Linear whose column halves are q and k; the kernels read them in place and write grad_q and
+    grad_k as the halves of one gradient for it."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, p_drop):
+        joint = k is None
+        q, v = _mha_operand(q, 'q'), _mha_operand(v, 'v')
+        if joint:
+            qk = q.contiguous()
+            c = qk.shape[-1] // 2
+            q, k = qk[..., :c], qk[..., c:]
+        else:
+            k = _mha_operand(k, 'k').to(q.dtype)
+        v = v.to(q.dtype)
+        nq, bs, c = q.shape
+        nk = k.shape[0]
+        assert k.shape == (nk, bs, c) and v.shape == (nk, bs, c) and c % heads == 0
+        (q, ldq), (k, ldk), (v, ldv) = _row_pitch(q), _row_pitch(k), _row_pitch(v)
+        out = torch.empty(nq, bs, c, dtype=q.dtype, device=q.device)
+        lse = torch.empty(bs, heads, nq, dtype=torch.float32, device=q.device)
+        seed = torch.randint(0, 2 ** 62, (1,), device=q.device, dtype=torch.int64) if p_drop > 0 else None
+        dt = 1 if q.dtype == torch.bfloat16 else 0
+        _launch('ver_mha_forward', lambda: lib().ver_mha_forward(
+            _p(q), _p(k), _p(v), dt, ldq, ldk, ldv, _p(seed), p_drop, _p(out), _p(lse), bs, heads, c // heads, nq, nk,
+            _stream()))
+        saved = (qk, v) if joint else (q, k, v)
+        ctx.save_for_backward(*saved, lse, seed if seed is not None else torch.empty(0, device=q.device))
+        ctx.heads, ctx.p_drop, ctx.joint = heads, p_drop, joint
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        # (an empty query set launches nothing: only then is there something to clear)
+        if ctx.joint:
+            qk, v, lse, seed = ctx.saved_tensors
+            c = qk.shape[-1] // 2
+            q, k = qk[..., :c], qk[..., c:]
+            gqk = torch.empty_like(qk)
+            gq, gk = gqk[..., :c], gqk[..., c:]
+        else:
+            q, k, v, lse, seed = ctx.saved_tensors
+            new = torch.empty if q.numel() else torch.zeros
+            gq, gk = new(q.shape, dtype=q.dtype, device=q.device), new(k.shape, dtype=q.dtype, device=q.device)
+        nq, bs, c = q.shape
+        nk = k.shape[0]
+        (q, ldq), (k, ldk), (v, ldv) = _row_pitch(q), _row_pitch(k), _row_pitch(v)      # (copies were made in forward)
+        go = _gpu(grad_out, 'grad_out').to(q.dtype).contiguous()
+        gv = (torch.empty if q.numel() else torch.zeros)(nk, bs, c, dtype=q.dtype, device=q.device)
+        ldg = 2 * c if ctx.joint else c
+        _launch('ver_mha_backward', lambda: lib().ver_mha_backward(
+            _p(q), _p(k), _p(v), 1 if q.dtype == torch.bfloat16 else 0, ldq, ldk, ldv, _p(go), _p(lse),
+            _p(seed) if ctx.p_drop > 0 else None, ctx.p_drop, _p(gq), _p(gk), _p(gv), ldg, ldg, c, bs, ctx.heads,
+            c // ctx.heads, nq, nk, _stream()))
+        if ctx.joint:
+            return gqk, None, gv, None, None
+        return gq, gk, gv, None, None
+
+
+def mha_core(q, k, v, heads, p_drop=0.0):
+    """softmax(q k^T / sqrt(head_dim)) (with dropout ``p_drop`` on the probabilities) times v, per head: q [Nq, B, C], k and v
+    [Nk, B, C], fp32 or bf16 -> [Nq, B, C] in q's dtype.  Views with a last-dimension stride of 1 and a uniform row pitch
+    (the column halves of one [N, B, 2C] Linear output) are read in place, anything else is made contiguous.  A shape
+    outside the library's range raises with its message."""
+    return MultiheadAttentionCoreFunction.apply(q, k, v, int(heads), float(p_drop))
+
+
+def mha_core_joint(qk, v, heads, p_drop=0.0):
+    """``mha_core(qk[..., :C], qk[..., C:], v, heads, p_drop)`` for the [N, B, 2C] output of one Linear, with grad_q and grad_k
+    written as the halves of ONE gradient for ``qk`` (autograd would otherwise pad each half's gradient to the full width
+    and add the two)."""
+    return MultiheadAttentionCoreFunction.apply(qk, None, v, int(heads), float(p_drop))
+
+
+# ------------------------------------------------------------------------------------------
 def occ_predict(logits, threshold=0.25):
     """Sparse occupancy prediction (ver_occ_predict; head:1505-1540): logits fp32|bf16 [N, C] ->
     int64 [K, 2] pairs (row index, class) of the rows whose best class probability reaches ``threshold``,

@@ -172,12 +172,21 @@ class VoxelCustomMSDeformableAttention(BaseModule):
 
 class MultiheadAttention(BaseModule):
     """mmcv 1.4.0 wrapper over nn.MultiheadAttention: q += query_pos,
-    k += key_pos (= query_pos when shapes match), identity + dropout(out)."""
+    k += key_pos (= query_pos when shapes match), identity + dropout(out).
+
+    ``fused``: True runs the attention between the input projections and ``out_proj`` as ``hipops.mha_core`` (one launch
+    each way, q and k from one GEMM where key and query are the same tensor; no head-averaged weights), False keeps
+    ``nn.MultiheadAttention``'s own route, None = the class attribute ``fused_attention``.  Parameters, state dict and config
+    are the same either way.  A fused request that cannot be honoured (masks, CPU tensors, a shape outside the kernels'
+    range, ...) raises."""
+
+    fused_attention = False
 
     def __init__(self, embed_dims, num_heads, attn_drop=0., proj_drop=0.,
                  dropout_layer=dict(type='Dropout', drop_prob=0.), init_cfg=None, batch_first=False,
-                 **kwargs):
+                 fused=None, **kwargs):
         super().__init__(init_cfg)
+        self.fused = fused
         if 'dropout' in kwargs:
             attn_drop = kwargs['dropout']
             dropout_layer = dict(type='Dropout', drop_prob=kwargs.pop('dropout'))
@@ -200,14 +209,18 @@ class MultiheadAttention(BaseModule):
             identity = query
         if key_pos is None and query_pos is not None and query_pos.shape == key.shape:
             key_pos = query_pos
+        same_qk = key is query and key_pos is query_pos          # q and k are then one tensor's two projections
         if query_pos is not None:
             query = query + query_pos
         if key_pos is not None:
             key = key + key_pos
         if self.batch_first:
             query, key, value = (t.transpose(0, 1) for t in (query, key, value))
-        out = self.attn(query=query, key=key, value=value, attn_mask=attn_mask,
-                        key_padding_mask=key_padding_mask)[0]
+        if self.fused_attention if self.fused is None else self.fused:
+            out = self._fused_attention(query, key, value, same_qk, attn_mask, key_padding_mask)
+        else:
+            out = self.attn(query=query, key=key, value=value, attn_mask=attn_mask,
+                            key_padding_mask=key_padding_mask)[0]
         if self.batch_first:
             out = out.transpose(0, 1)
         if defer_residual and (not self.training or self.proj_drop.p == 0.0):
@@ -215,6 +228,42 @@ class MultiheadAttention(BaseModule):
             p = drop.p if (isinstance(drop, nn.Dropout) and drop.training) else 0.0
             return PendingResidual(out.contiguous(), identity, p)
         return identity + self.dropout_layer(self.proj_drop(out))
+
+    def _fused_attention(self, query, key, value, same_qk, attn_mask, key_padding_mask):
+        """Sequence-first query [Nq, B, C], key / value [Nk, B, C] (positions added) -> out_proj(attention), with
+        ``hipops.mha_core`` between the in-projection Linears and ``out_proj``.  ``same_qk``: key holds the query's values
+        (one tensor, one positional add): q and k then come out of ONE [2C, C] GEMM and go to the kernel as its column halves."""
+        attn = self.attn
+
+        def refuse(why):
+            raise RuntimeError('MultiheadAttention(fused=True) cannot take this call: %s' % why)
+
+        if not (query.is_cuda and key.is_cuda and value.is_cuda):
+            refuse('the fused attention runs only on the GPU (HIP kernels); there is no CPU fallback in this package')
+        if attn_mask is not None:
+            refuse('attn_mask is not supported')
+        if key_padding_mask is not None:
+            refuse('key_padding_mask is not supported')
+        if not attn._qkv_same_embed_dim:
+            refuse('kdim / vdim differ from embed_dim (no packed in_proj_weight)')
+        if attn.bias_k is not None or attn.bias_v is not None or attn.add_zero_attn:
+            refuse('bias_k / bias_v / add_zero_attn are not supported')
+        from ..hipops import mha_core, mha_core_joint, mha_supported
+        nq, bs, c = query.shape
+        nk = key.shape[0]
+        heads = attn.num_heads
+        if not mha_supported(bs, heads, c // heads, nq, nk):
+            refuse('shape (B %d, heads %d, head_dim %d, Nq %d, Nk %d) is outside the supported range of ver_mha_* '
+                   '(Nq, Nk <= 128; head_dim a multiple of 8 up to 128)' % (bs, heads, c // heads, nq, nk))
+        w, b = attn.in_proj_weight, attn.in_proj_bias
+        bias = (lambda lo, hi: None) if b is None else (lambda lo, hi: b[lo:hi])
+        p_drop = attn.dropout if attn.training else 0.0
+        v = F.linear(value, w[2 * c:], bias(2 * c, 3 * c))
+        if same_qk:                             # the kernels read q and k as the column halves of the one GEMM's output
+            out = mha_core_joint(F.linear(query, w[:2 * c], bias(0, 2 * c)), v, heads, p_drop)
+        else:
+            out = mha_core(F.linear(query, w[:c], bias(0, c)), F.linear(key, w[c:2 * c], bias(c, 2 * c)), v, heads, p_drop)
+        return attn.out_proj(out)
 
 
 class DetrTransformerDecoderLayer(MyCustomBaseTransformerLayer):
