@@ -561,7 +561,7 @@ int ver_occ_mlp_classes(const void* x, const void* image, const float* vectors, 
  *   workspace  f32 [splits, Ka, N]: the row axis is split into `splits` chunks (0: ver_wgrad_tn_splits), every
  *              chunk's product stays fp32 until the chunks are added up (no bf16 rounding of partial sums)
  * Requirements: a, g 16-byte aligned, lda % 8 == 0, ldg % 8 == 0, N % 4 == 0, ldo % 4 == 0; any M (M = 0: zeros).
- * flags: 0 (the prefetch-distance / slabs-per-phase experiments of the 32x32x16 body are fixed per MFMA shape in ver_wgrad.hip).
+ * flags: 0 (slabs per phase and the prefetch distance are constants of ver_wgrad.hip).
  */
 int  ver_wgrad_tn_splits(long M, int Ka, int N);
 /*   the same choice knowing the widest row pitch ld = max(lda, ldg) in elements (ABI 29): a row chunk has to stay inside the

@@ -1,5 +1,5 @@
-"""The fragment and accumulator maps of the two GEMM bodies (csrc/ver_gemm.hip, csrc/ver_wgrad.hip), whatever MFMA shape they
-are built with.  Needs an MI355X: run with ``-m gpu``.
+"""The fragment and accumulator maps of the two GEMM bodies (csrc/ver_gemm.hip, csrc/ver_wgrad.hip) on the one MFMA shape
+they run, v_mfma_f32_16x16x32_bf16 (csrc/ver_gemm_tile.h).  Needs an MI355X: run with ``-m gpu``.
 
 * Exact arithmetic.  Operands are integers in [-4, 4] held in bf16: every product (|.| <= 16) and every fp32 partial sum
   (|.| <= 16 K < 2^24, asserted on the CPU before a launch) is exact in any summation order, so the result must EQUAL the
@@ -132,6 +132,18 @@ def test_wgrad_tn_is_exact_on_small_integers(splits, dtype):
         assert torch.equal(got.double(), ref)
     else:
         assert torch.equal(got, _round_bf16(ref))
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['fp32', 'bf16'])
+@pytest.mark.parametrize('splits', [1, 8])
+def test_wgrad_tn_without_rows_writes_zeros(splits, dtype):
+    """M = 0, Ka = N = 64: no product kernel -- the launcher's tail zero-fills the ``splits`` partial tiles and the reduce
+    writes the 64 x 64 result over what was there, for one chunk too (nothing is stored directly without rows)."""
+    hip = _hip()
+    out = torch.full((64, 64), 7.0, dtype=dtype, device=DEV)
+    got = hip.wgrad_tn(torch.zeros(0, 64, dtype=torch.bfloat16, device=DEV), torch.zeros(0, 64, dtype=torch.bfloat16, device=DEV),
+                       out=out, out_dtype=dtype, splits=splits)
+    assert got is out and torch.equal(out, torch.zeros(64, 64, dtype=dtype, device=DEV))
 
 
 # --------------------------------------------------------------------------------------------- implicit forms

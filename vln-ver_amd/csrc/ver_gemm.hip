@@ -25,79 +25,17 @@
 //     ver_gemm_nn_splitk); tiles are dealt to the XCDs in contiguous
 //     ranges, the N tiles of one row block next to each other, so that the 32 tiles in flight on an XCD share their A
 //     rows and W columns in its L2.
-// MFMA shape: v_mfma_f32_16x16x32_bf16 (kShape; the v_mfma_f32_32x32x16_bf16 form, two k-steps of 4 x 2 tiles per phase,
-// is the body's other value).  With the tap stream as it was first written -- the lane's two offsets in scratch memory, read
-// back in front of the A requests of every phase, and the tap tables read by dependent vector loads at every switch -- the
-// implicit forms lost 17-31 % on 16x16x32; with the stream in registers both shapes gain, 16x16x32 more (DESIGN.md 3.3,
-// profiles/gemm_tap_stream_ab.jsonl).  Implicit and explicit entry points are compared bit for bit and share the shape.
-#include "ver_common.h"
+// The MFMA shape, the fragment reads, the swizzles and the lattice addressing are ver_gemm_tile.h's, shared with ver_wgrad.hip.
+// (The body this kernel was first written on, two k-steps of the other bf16 MFMA shape per phase, lost both A/B rounds of
+// DESIGN.md 3.3 and lies in scratch/experiments/k_gemm_nn_mfma32.hip.inc.)  Implicit and explicit entry points are compared
+// bit for bit.
+#include "ver_gemm_tile.h"
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-
-constexpr int kTile = 256;
+using namespace gemm_tile;
 constexpr int kStageBytes = 32768;          // A image [256][32] (16 KB) + two W slabs [16][256] (2 x 8 KB)
 constexpr int kStages = 4;
 constexpr int kLdsBytes = kStages * kStageBytes;
-
-// MFMA shape of the body (compile time, as in ver_wgrad.hip): 32 = v_mfma_f32_32x32x16_bf16, two k-steps of 4 x 2 tiles per
-// phase; 16 = v_mfma_f32_16x16x32_bf16, ONE k-step of 8 x 4 tiles per phase (k-groups 0-1 from W slab 0, 2-3 from slab 1).
-constexpr int kShape = 16;
-template <int SH>
-struct Shape {
-    typedef f32x16 acc_t;
-    static constexpr int NI = 4, NJ = 2, NR = 16, TW = 32;
-    // accumulator register r of a lane: row reg_row(r) + lane_row(lane) of the tile, column lane & (TW - 1)
-    static __device__ __forceinline__ int reg_row(int r) { return (r & 3) + 8 * (r >> 2); }
-    static __device__ __forceinline__ int lane_row(int lane) { return 4 * (lane >> 5); }
-    // A image (64-byte rows): position p of row `row` holds source chunk p ^ swz_a(row).  Lane (i = l & 31, k half l >> 5)
-    // reads chunk (2 step + (l >> 5)) of row i: every 16-lane group of a ds_read_b128 covers the 16 slots of a bank row
-    static __device__ __forceinline__ int swz_a(int row) { return (row >> 2) & 3; }
-    // W slab piece (8 rows x 128 B) of row group `rowhalf`: position p of row `row` holds chunk p ^ swz_w (ver_wgrad.hip)
-    static __device__ __forceinline__ int swz_w(int row, int rowhalf) { return ((row >> 1) & 1) << 2; }
-};
-template <>
-struct Shape<16> {
-    typedef f32x4 acc_t;
-    static constexpr int NI = 8, NJ = 4, NR = 4, TW = 16;
-    static __device__ __forceinline__ int reg_row(int r) { return r; }
-    static __device__ __forceinline__ int lane_row(int lane) { return 4 * (lane >> 4); }
-    // lane (i = l & 15, k-group c = l >> 4) reads chunk c of row i.  The 16-lane groups of a ds_read_b128 are lanes {0-3,
-    // 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32: per row-in-four, a group holds (c, row quarter h = i >> 2) =
-    // (0, 0), (0, 3), (1, 1), (1, 2) -- or (1, 0), (1, 3), (0, 1), (0, 2) -- whose positions c ^ f(h) must differ:
-    // f = (0, 3, 2, 1) = -h gives {0, 1, 2, 3}
-    static __device__ __forceinline__ int swz_a(int row) { return (0 - (row >> 2)) & 3; }
-    // the two 16-lane groups of a half read the SAME 16 columns of rows 0-7 and 8-15 of a slab, 4 KiB apart: rows 8-15 swap
-    // their 32-byte column pairs and the half covers all 64 banks (ver_wgrad.hip)
-    static __device__ __forceinline__ int swz_w(int row, int rowhalf) { return (((row >> 1) & 1) << 2) ^ (rowhalf << 1); }
-};
-typedef Shape<kShape> sh;
-static_assert(Shape<32>::NI * Shape<32>::TW == 128 && Shape<32>::NJ * Shape<32>::TW == 64 && Shape<32>::NI * Shape<32>::NJ * Shape<32>::NR == 128 &&
-                  Shape<16>::NI * Shape<16>::TW == 128 && Shape<16>::NJ * Shape<16>::TW == 64 && Shape<16>::NI * Shape<16>::NJ * Shape<16>::NR == 128,
-              "a wave tile is 128 x 64 in 128 accumulator registers");
-
-// LDS reads as inline asm: behind the builtins the compiler waits for vmcnt(0) in front of every LDS read that follows an
-// LDS-DMA (ver_wgrad.hip).  Results are valid behind the s_waitcnt lgkmcnt(0) of phase().
-template <int OFF>
-__device__ __forceinline__ i32x2 tr_read(int addr) {
-    i32x2 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-template <int OFF>
-__device__ __forceinline__ i32x4 row_read(int addr) {
-    i32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-__device__ __forceinline__ bf16x8 frag(i32x2 lo, i32x2 hi) {
-    return __builtin_bit_cast(bf16x8, (i32x4)__builtin_shufflevector(lo, hi, 0, 1, 2, 3));
-}
 
 // Implicit operand (ver_gemm_nn_taps): A is never materialised -- row r of the product is cell (b, zl, y, x) of a Z = 4
 // lattice (r = ((b 2 + zl) H + y) W + x), its K axis `ntaps` blocks of C channels, block t = the C-vector of the neighbouring
@@ -134,32 +72,13 @@ struct GemmArgs {
 };
 
 struct GemmLane {
-    int offA0, offA1;       // A fragment reads (stage 0, row tile 0): 32x32x16 k-step 0 / 1 of a phase; 16x16x32: offA0 only
-    int offB[4];            // W fragment reads (stage 0): 32x32x16 slab 0, column tile 0 / 1; 16x16x32: the four 16-column
-                            // tiles, in the lane's slab and row half
+    int offA0;              // A fragment reads (stage 0, row tile 0)
+    int offB[4];            // W fragment reads (stage 0): the four 16-column tiles, in the lane's slab and row half
     int voA, voW;           // per-lane source offsets of this wave's LDS-DMA pieces
     int stepW;              // bytes per 16-row slab of W
     int stepA16;            // bytes per 16 rows of A (second LDS-DMA piece of a wave)
     int dmaA, dmaW;         // offsets of this wave's pieces inside a stage
 };
-
-// byte offset of the C-vector of cell (b, z = zl + dz, y, x) in a source lattice of layout L (ver_lattice_gather's layouts:
-// 0 plain [B,4,H,W,C], 2 z-split [B,2,H,W,2,C], 3 planar z-split [4,B,2,H/2,W/2,2,C]); outside the lattice: an offset
-// beyond every buffer range (the DMA then writes zeros).  All lattices here are < 2 GiB (checked by the launcher).
-constexpr int kOutside = (int)0x80000000;
-template <int L>
-__device__ __forceinline__ int cell_off(const TapArgs& t, int b, int zl, int y, int x, int dz) {
-    if ((unsigned)y >= (unsigned)t.H || (unsigned)x >= (unsigned)t.W || b < 0) return kOutside;
-    const int j = dz >> 1;                                  // z = zl + dz, dz in {0, 2}: same zl, upper half j
-    int v;
-    if (L == 0)
-        v = ((b * 4 + zl + dz) * t.H + y) * t.W + x;
-    else if (L == 2)
-        v = ((((b * 2 + zl) * t.H + y) * t.W + x) << 1) + j;
-    else
-        v = (((((((y & 1) << 1 | (x & 1)) * t.B + b) * 2 + zl) * (t.H >> 1) + (y >> 1)) * (t.W >> 1) + (x >> 1)) << 1) + j;
-    return v * t.C * 2;
-}
 
 struct TapLane {                // implicit operand, per lane (VGPRs): the lane's two rows and their current source offsets
     int b1, zl1, y1, x1, b2, zl2, y2, x2;
@@ -201,8 +120,9 @@ __device__ __forceinline__ void tap_begin(const TapArgs& t, TapLane& tl, TapWave
         if (tl.b2 >= 0) o2 = (tl.pos2 * t.ncst + dz) * t.CW * 2 + tl.chunk;
         ra = rcst;
     } else if (live) {
-        const int c1 = cell_off<L>(t, tl.b1, tl.zl1, tl.y1 + dy, tl.x1 + dx, dz);
-        const int c2 = cell_off<L>(t, tl.b2, tl.zl2, tl.y2 + dy, tl.x2 + dx, dz);
+        const LatticeGeom geom = {t.B, t.H, t.W, t.C};
+        const int c1 = cell_off<L>(geom, tl.b1, tl.zl1, tl.y1 + dy, tl.x1 + dx, dz);
+        const int c2 = cell_off<L>(geom, tl.b2, tl.zl2, tl.y2 + dy, tl.x2 + dx, dz);
         if (c1 != kOutside) o1 = c1 + tl.chunk;
         if (c2 != kOutside) o2 = c2 + tl.chunk;
         ra = __builtin_amdgcn_make_buffer_rsrc((void*)(t.lattice + (long)pl * t.plane_elems), 0,
@@ -237,7 +157,7 @@ __device__ __forceinline__ void request_a(char* dst, const GemmLane& c, __amdgpu
     }
 }
 
-// 16x16x32: one phase = ONE k-step of 32: 8 row reads (the lane's chunk of its row in the eight 16-row tiles), 8 transposing
+// one phase = ONE k-step of 32: 8 row reads (the lane's chunk of its row in the eight 16-row tiles), 8 transposing
 // reads (4 column tiles, k halves lo / hi of the lane's slab and row group), the LDS-DMA of the phase two ahead, 32 MFMAs.
 template <int ST, int IMPL>
 __device__ __forceinline__ void phase(char* lds, f32x4 (&acc)[8][4], const GemmLane& c, __amdgpu_buffer_rsrc_t& ra,
@@ -289,69 +209,6 @@ __device__ __forceinline__ void phase(char* lds, f32x4 (&acc)[8][4], const GemmL
     __builtin_amdgcn_s_barrier();
 }
 
-// 32x32x16: one phase = two k-steps of 16 (8 + 8 fragment reads, 16 MFMAs on 4 x 2 tiles)
-template <int ST, int IMPL>
-__device__ __forceinline__ void phase(char* lds, f32x16 (&acc)[4][2], const GemmLane& c, __amdgpu_buffer_rsrc_t& ra,
-                                      __amdgpu_buffer_rsrc_t rw, int& soA, int& soW, const TapArgs& t, TapLane& tl, TapWave& ts,
-                                      __amdgpu_buffer_rsrc_t rcst) {
-    constexpr int SB = (ST & 1) * kStageBytes;
-    constexpr int UP = ST >= 2 ? 65536 : 0;
-    const int a0 = c.offA0 + UP, a1 = c.offA1 + UP, b0 = c.offB[0] + UP, b1 = c.offB[1] + UP;
-    i32x4 av[2][4];
-    i32x2 bl[2][2], bh[2][2];
-    // k-step 0: A chunks (l >> 5), W slab 0; k-step 1: A chunks 2 + (l >> 5), W slab 1
-    av[0][0] = row_read<SB>(a0);
-    av[0][1] = row_read<SB + 2048>(a0);
-    bl[0][0] = tr_read<SB + 16384>(b0);
-    bh[0][0] = tr_read<SB + 16384 + 512>(b0);
-    bl[0][1] = tr_read<SB + 16384>(b1);
-    bh[0][1] = tr_read<SB + 16384 + 512>(b1);
-    av[0][2] = row_read<SB + 4096>(a0);
-    av[0][3] = row_read<SB + 6144>(a0);
-    av[1][0] = row_read<SB>(a1);
-    av[1][1] = row_read<SB + 2048>(a1);
-    bl[1][0] = tr_read<SB + 24576>(b0);
-    bh[1][0] = tr_read<SB + 24576 + 512>(b0);
-    bl[1][1] = tr_read<SB + 24576>(b1);
-    bh[1][1] = tr_read<SB + 24576 + 512>(b1);
-    av[1][2] = row_read<SB + 4096>(a1);
-    av[1][3] = row_read<SB + 6144>(a1);
-    // LDS-DMA of the phase two ahead: this wave's 2 x 16 rows of the A image and its piece of each W slab
-    constexpr int DS = ((ST + 2) % kStages) * kStageBytes;
-    request_a<IMPL, false>(lds + DS + c.dmaA, c, ra, rcst, soA, t, tl, ts);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_void*)(lds + DS + 16384 + c.dmaW), 16, c.voW, soW, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_void*)(lds + DS + 24576 + c.dmaW), 16, c.voW, soW + c.stepW, 0, 0);
-    soW += 2 * c.stepW;
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // this wave's pieces of the NEXT phase have landed
-    __builtin_amdgcn_s_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(av[0][0]), "+v"(av[0][1]), "+v"(av[0][2]), "+v"(av[0][3]), "+v"(av[1][0]), "+v"(av[1][1]), "+v"(av[1][2]),
-                   "+v"(av[1][3]), "+v"(bl[0][0]), "+v"(bh[0][0]), "+v"(bl[0][1]), "+v"(bh[0][1]), "+v"(bl[1][0]), "+v"(bh[1][0]),
-                   "+v"(bl[1][1]), "+v"(bh[1][1])
-                 :
-                 : "memory");
-    if constexpr (IMPL >= 0) asm volatile("" : "+s"(ts.next));      // (a descriptor requested in this phase: valid from here)
-    bf16x8 a[2][4], b[2][2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) a[u][i] = __builtin_bit_cast(bf16x8, av[u][i]);
-        b[u][0] = frag(bl[u][0], bh[u][0]);
-        b[u][1] = frag(bl[u][1], bh[u][1]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int it = 0; it < 4; ++it)
-#pragma unroll
-            for (int jt = 0; jt < 2; ++jt)
-                acc[it][jt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[u][it], b[u][jt], acc[it][jt], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-}
 
 template <int IMPL>
 __global__ __launch_bounds__(512) void k_gemm_nn(GemmArgs p) {
@@ -384,40 +241,27 @@ __global__ __launch_bounds__(512) void k_gemm_nn(GemmArgs p) {
         // A image piece: 16 rows x 64 B per instruction; lane -> (row l >> 2, position l & 3), position p holds source
         // chunk p ^ Shape::swz_a(row).  This wave moves rows 32 w .. 32 w + 31 (two instructions, + 16 rows = + 1 KiB).
         const int prow = 32 * wave + (lane >> 2);
-        const int pch = (lane & 3) ^ sh::swz_a(prow & 15);
+        const int pch = (lane & 3) ^ Shape::swz_a(prow & 15);
         c.voA = (int)(prow * p.lda * 2) + pch * 16;
         c.dmaA = wave * 2048;
         c.stepA16 = (int)(16 * p.lda * 2);          // (second instruction: rows + 16; same swizzle term)
-        // W slab piece: 8 rows x 128 B, chunks XOR-ed by Shape::swz_w (ver_wgrad.hip)
-        const int wrow = lane >> 3, wch = (lane & 7) ^ sh::swz_w(wrow, wave >> 2);
+        // W slab piece: 8 rows x 128 B, chunks XOR-ed by Shape::swz
+        const int wrow = lane >> 3, wch = (lane & 7) ^ Shape::swz(wrow, wave >> 2);
         c.voW = (int)(((8 * (wave >> 2) + wrow) * p.ldw + 64 * (wave & 3)) * 2) + wch * 16;
         c.stepW = (int)(16 * p.ldw * 2);
         c.dmaW = wave * 1024;
     }
-    // fragment reads.  32x32x16 -- A (row mode): lane (i = l & 31, k half = l >> 5) reads chunk (2 step + (l >> 5)) ^ swz_a(i)
-    // of row 128 wr + 32 it + i;  W (transposing): as in ver_wgrad.hip.  16x16x32 -- A: lane (i = l & 15, k-group g = l >> 4)
-    // reads chunk g ^ swz_a(i) of row 128 wr + 16 it + i;  W: group g reads rows 8 (g & 1) .. + 7 of slab g >> 1, lane c of
-    // it row c >> 2 (and + 4), chunk 2 q + ((c & 3) >> 1) of column tile q, half c & 1
+    // fragment reads.  A (row mode): lane (i = l & 15, k-group g = l >> 4) reads chunk g ^ swz_a(i) of row 128 wr + 16 it + i;
+    // W (transposing): group g reads rows 8 (g & 1) .. + 7 of slab g >> 1, lane c of it row c >> 2 (and + 4), chunk
+    // 2 q + ((c & 3) >> 1) of column tile q, half c & 1
     {
         const int lbase = (int)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
-        if constexpr (kShape == 32) {
-            const int i = lane & 31;
-            c.offA0 = lbase + (128 * wr + i) * 64 + (((lane >> 5) ^ sh::swz_a(i & 15)) << 4);
-            c.offA1 = c.offA0 ^ 32;
-            const int q = lane >> 4, cl = lane & 15;
-            const int lowch = (2 * (q & 1) + ((cl & 3) >> 1)) ^ sh::swz_w(cl >> 2, q >> 1);
-            c.offB[0] = lbase + ((q >> 1) * 32 + (cl >> 2)) * 128 + lowch * 16 + (cl & 1) * 8 + wc * 1024;
-            c.offB[1] = c.offB[0] ^ 64;
-            c.offB[2] = c.offB[3] = 0;
-        } else {
-            const int i = lane & 15, g = lane >> 4;
-            c.offA0 = lbase + (128 * wr + i) * 64 + ((g ^ sh::swz_a(i)) << 4);
-            c.offA1 = 0;
+        const int i = lane & 15, g = lane >> 4;
+        c.offA0 = lbase + (128 * wr + i) * 64 + ((g ^ Shape::swz_a(i)) << 4);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int ch = (2 * q + ((i & 3) >> 1)) ^ sh::swz_w(i >> 2, g & 1);
-                c.offB[q] = lbase + (g >> 1) * 8192 + (g & 1) * 4096 + (i >> 2) * 128 + ch * 16 + (i & 1) * 8 + wc * 1024;
-            }
+        for (int q = 0; q < 4; ++q) {
+            const int ch = (2 * q + ((i & 3) >> 1)) ^ Shape::swz(i >> 2, g & 1);
+            c.offB[q] = lbase + (g >> 1) * 8192 + (g & 1) * 4096 + (i >> 2) * 128 + ch * 16 + (i & 1) * 8 + wc * 1024;
         }
     }
     TapLane tl = {};
@@ -442,7 +286,7 @@ __global__ __launch_bounds__(512) void k_gemm_nn(GemmArgs p) {
         decode(row0 + prow + 16, tl.b2, tl.zl2, tl.y2, tl.x2);
         tl.pos1 = (tl.zl1 * p.t.H + tl.y1) * p.t.W + tl.x1;
         tl.pos2 = (tl.zl2 * p.t.H + tl.y2) * p.t.W + tl.x2;
-        tl.chunk = ((lane & 3) ^ sh::swz_a(prow & 15)) * 16;
+        tl.chunk = ((lane & 3) ^ Shape::swz_a(prow & 15)) * 16;
         // (the kernel's one parameter starts the kernel-argument block)
         ts.tab = (const __attribute__((address_space(4))) unsigned*)((const __attribute__((address_space(4))) char*)
                      __builtin_amdgcn_kernarg_segment_ptr() + offsetof(GemmArgs, t) + offsetof(TapArgs, desc));
@@ -452,13 +296,13 @@ __global__ __launch_bounds__(512) void k_gemm_nn(GemmArgs p) {
         tap_begin<IMPL>(p.t, tl, ts, d, ra, rcst);
         desc_ready(ts.next);
     }
-    sh::acc_t acc[sh::NI][sh::NJ];
+    Shape::acc_t acc[Shape::NI][Shape::NJ];
 #pragma unroll
-    for (int it = 0; it < sh::NI; ++it)
+    for (int it = 0; it < Shape::NI; ++it)
 #pragma unroll
-        for (int jt = 0; jt < sh::NJ; ++jt)
+        for (int jt = 0; jt < Shape::NJ; ++jt)
 #pragma unroll
-            for (int r = 0; r < sh::NR; ++r) acc[it][jt][r] = 0.0f;
+            for (int r = 0; r < Shape::NR; ++r) acc[it][jt][r] = 0.0f;
 
     int soA = 0, soW = 0;
     // prologue: phases 0 and 1 in flight, phase 0 landed
@@ -490,60 +334,60 @@ __global__ __launch_bounds__(512) void k_gemm_nn(GemmArgs p) {
     if (p.S > 1) {
         // partial tile of this K slice -> workspace (fp32, [S][M][N]); bias and rounding happen in k_gemm_reduce
         float* out = p.ws + (long)split * p.M * p.N;
-        const long i0 = row0 + 128 * wr + sh::lane_row(lane);
-        const int j0 = nt * kTile + 64 * wc + (lane & (sh::TW - 1));
+        const long i0 = row0 + 128 * wr + Shape::lane_row(lane);
+        const int j0 = nt * kTile + 64 * wc + (lane & (Shape::TW - 1));
 #pragma unroll
-        for (int it = 0; it < sh::NI; ++it)
+        for (int it = 0; it < Shape::NI; ++it)
 #pragma unroll
-            for (int jt = 0; jt < sh::NJ; ++jt) {
-                const int j = j0 + sh::TW * jt;
+            for (int jt = 0; jt < Shape::NJ; ++jt) {
+                const int j = j0 + Shape::TW * jt;
 #pragma unroll
-                for (int r = 0; r < sh::NR; ++r) {
-                    const long i = i0 + sh::TW * it + sh::reg_row(r);
+                for (int r = 0; r < Shape::NR; ++r) {
+                    const long i = i0 + Shape::TW * it + Shape::reg_row(r);
                     if (i < p.M && j < p.N) out[i * p.N + j] = acc[it][jt][r];
                 }
             }
         return;
     }
-    // C tile: register r of tile (it, jt) is row reg_row(r) + lane_row(lane), column lane & (TW - 1) of the tile (32x32x16:
-    // (r & 3) + 8 (r >> 2) + 4 (lane >> 5), lane & 31; 16x16x32: r + 4 (lane >> 4), lane & 15).  Buffer stores: one 32-bit lane
-    // offset + a scalar row offset per store; rows past M fall outside the range and are dropped, columns past N are sent
-    // there on purpose.
+    // C tile: register r of tile (it, jt) is row r + 4 (lane >> 4), column lane & 15 of the tile (Shape::reg_row / lane_row).
+    // Buffer stores: one 32-bit lane offset + a scalar row offset per store; rows past M fall outside the range and are
+    // dropped, columns past N are sent there on purpose.
     __bf16* cb = p.C + row0 * p.ldc + (long)nt * kTile;
     const long cbytes = ((p.M - row0 - 1) * p.ldc + p.N - (long)nt * kTile) * 2;
     const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)cb, 0, (int)max(0L, min(cbytes, 0xFFFFFFFFL)), 0x00020000);
     const int ldc2 = (int)(p.ldc * 2);
-    const int vbase = (128 * wr + sh::lane_row(lane)) * ldc2 + (64 * wc + (lane & (sh::TW - 1))) * 2;
+    const int vbase = (128 * wr + Shape::lane_row(lane)) * ldc2 + (64 * wc + (lane & (Shape::TW - 1))) * 2;
     // implicit operand: + rowpos[row % P][j], the position-dependent constant part of the row's result (rows of a tile are
     // consecutive: one conditional subtraction per row instead of a division)
     const bool haspos = IMPL >= 0 && p.t.rowpos != nullptr;
-    const int pos0 = haspos ? (int)((row0 + 128 * wr + sh::lane_row(lane)) % p.t.P) : 0;
+    const int pos0 = haspos ? (int)((row0 + 128 * wr + Shape::lane_row(lane)) % p.t.P) : 0;
 #pragma unroll
-    for (int jt = 0; jt < sh::NJ; ++jt) {
-        const int j = nt * kTile + 64 * wc + sh::TW * jt + (lane & (sh::TW - 1));
+    for (int jt = 0; jt < Shape::NJ; ++jt) {
+        const int j = nt * kTile + 64 * wc + Shape::TW * jt + (lane & (Shape::TW - 1));
         const float bj = (p.bias && j < p.N) ? p.bias[j] : 0.0f;
-        const int vo = j < p.N ? vbase + 2 * sh::TW * jt : -2;
+        const int vo = j < p.N ? vbase + 2 * Shape::TW * jt : -2;
 #pragma unroll
-        for (int it = 0; it < sh::NI; ++it) {
-            float add[sh::NR];
+        for (int it = 0; it < Shape::NI; ++it) {
+            float add[Shape::NR];
 #pragma unroll
-            for (int r = 0; r < sh::NR; ++r) {
+            for (int r = 0; r < Shape::NR; ++r) {
                 add[r] = bj;
                 if (haspos) {
-                    int pp = pos0 + sh::TW * it + sh::reg_row(r);
+                    int pp = pos0 + Shape::TW * it + Shape::reg_row(r);
                     while (pp >= p.t.P) pp -= p.t.P;          // (at most once for P >= 256: the step's lattices have 450+)
-                    const long row = row0 + 128 * wr + sh::lane_row(lane) + sh::TW * it + sh::reg_row(r);
+                    const long row = row0 + 128 * wr + Shape::lane_row(lane) + Shape::TW * it + Shape::reg_row(r);
                     if (j < p.N && row < p.M) add[r] += p.t.rowpos[(long)pp * p.N + j];
                 }
             }
 #pragma unroll
-            for (int r = 0; r < sh::NR; ++r) {
+            for (int r = 0; r < Shape::NR; ++r) {
                 const __bf16 v = (__bf16)(acc[it][jt][r] + add[r]);
-                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(short, v), rc, vo, (sh::TW * it + sh::reg_row(r)) * ldc2, 0);
+                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(short, v), rc, vo, (Shape::TW * it + Shape::reg_row(r)) * ldc2, 0);
             }
         }
     }
 }
+
 // C[i][j] (bf16, row pitch ldc) = sum over the S partial products + bias[j]; 4 columns per thread (N % 4 == 0)
 __global__ __launch_bounds__(256) void k_gemm_reduce(const float* __restrict__ ws, const float* __restrict__ bias,
                                                      __bf16* __restrict__ c, long ldc, int S, long M, int N) {
@@ -627,9 +471,7 @@ extern "C" int ver_gemm_nn_splitk(const void* a, long lda, const void* w, long l
     p.ws = (float*)workspace;
     p.per_xcd = (p.T * p.S + 7) / 8;
     p.t = TapArgs{};
-    hipError_t e = hipFuncSetAttribute((const void*)k_gemm_nn<-1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_gemm_nn: LDS attribute: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(k_gemm_nn<-1>, dim3((unsigned)(8 * p.per_xcd)), dim3(512), kLdsBytes, st, p);
+    if (int rc = launch_tile_kernel("ver_gemm_nn", k_gemm_nn<-1>, p, 8 * p.per_xcd, kLdsBytes, st)) return rc;
     if (p.S > 1) {
         long grid = (M * N / 4 + 255) / 256;
         if (grid > 4096) grid = 4096;
@@ -663,9 +505,7 @@ extern "C" int ver_gemm_nn_planes(const void* lattice, int layout, int B, int H,
                                   const void* w, long ldw, const float* rowpos, const float* bias, void* c, long ldc, int N,
                                   void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    VER_REQUIRE(B >= 0 && H > 0 && W > 0 && C > 0 && N > 0 && ntaps > 0, VER_EINVAL, "ver_gemm_nn_taps: bad sizes");
-    VER_REQUIRE(layout == 0 || layout == 2 || layout == 3, VER_EINVAL, "ver_gemm_nn_taps: layout %d (0 plain, 2 z-split, 3 planar z-split)", layout);
-    VER_REQUIRE(layout != 3 || (H % 2 == 0 && W % 2 == 0), VER_EINVAL, "ver_gemm_nn_taps: planar needs even H, W");
+    if (int rc = check_lattice_args("ver_gemm_nn_taps", layout, B, H, W, C, N, ntaps)) return rc;
     if (B == 0) return VER_OK;
     VER_REQUIRE(lattice && taps && w && c, VER_EINVAL, "ver_gemm_nn_taps: null pointer argument");
     VER_REQUIRE(ntaps <= 64, VER_EUNSUPPORTED, "ver_gemm_nn_taps: %d taps (at most 64)", ntaps);
@@ -674,12 +514,7 @@ extern "C" int ver_gemm_nn_planes(const void* lattice, int layout, int B, int H,
     VER_REQUIRE(cst == nullptr || (ncst > 0 && ncst <= 64 && cw >= 32 && cw % 32 == 0 && ((uintptr_t)cst & 15) == 0), VER_EINVAL,
                 "ver_gemm_nn_segments: the constant-pattern table needs 1..64 blocks of a width that is a multiple of 32");
     long K = 0;
-    for (int i = 0; i < ntaps; ++i) {
-        const bool is_cst = taps[3 * i] < 0;                 // (-1 - block, 0, 0): a constant-pattern segment
-        VER_REQUIRE(!is_cst || (cst && -1 - taps[3 * i] < ncst), VER_EINVAL, "ver_gemm_nn_segments: segment %d names pattern block %d of %d",
-                    i, -1 - taps[3 * i], cst ? ncst : 0);
-        K += is_cst ? cw : C;
-    }
+    if (int rc = check_segments("ver_gemm_nn_segments", "ver_gemm_nn_taps", taps, ntaps, C, cst, ncst, cw, &K)) return rc;
     VER_REQUIRE(lbytes < 0x7FFFFFFFL, VER_EUNSUPPORTED, "ver_gemm_nn_taps: the source lattice (%ld bytes) exceeds the 2-GiB range of the tap offsets", lbytes);
     VER_REQUIRE(ldw >= N && ldc >= N && ldw % 8 == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)lattice & 15) == 0, VER_EUNSUPPORTED,
                 "ver_gemm_nn_taps: w must be 16-byte aligned with a row pitch that is a multiple of 8 elements");
@@ -716,25 +551,13 @@ extern "C" int ver_gemm_nn_planes(const void* lattice, int layout, int B, int H,
     for (int i = 0; i < ntaps; ++i) {
         VER_REQUIRE(!tap_plane || (tap_plane[i] >= 0 && tap_plane[i] < nplanes), VER_EINVAL, "ver_gemm_nn_planes: tap %d reads plane %d of %d", i,
                     tap_plane ? tap_plane[i] : 0, nplanes);
-        const int dz = taps[3 * i], dy = taps[3 * i + 1], dx = taps[3 * i + 2];
-        if (dz < 0) {
+        const int dz = taps[3 * i], dy = taps[3 * i + 1], dx = taps[3 * i + 2];     // (checked by check_segments)
+        if (dz < 0)
             p.t.desc[i] = 0x80000000u | (unsigned)(-1 - dz) << 16;
-            continue;
-        }
-        VER_REQUIRE((dz == 0 || dz == 2) && dy >= -64 && dy <= 64 && dx >= -64 && dx <= 64, VER_EINVAL,
-                    "ver_gemm_nn_taps: tap %d = (%d, %d, %d): dz must be 0 or 2", i, dz, dy, dx);
-        p.t.desc[i] = (unsigned)(tap_plane ? tap_plane[i] : 0) << 22 | (unsigned)dz << 16 | (unsigned)(dy & 0xFF) << 8 | (unsigned)(dx & 0xFF);
+        else
+            p.t.desc[i] = (unsigned)(tap_plane ? tap_plane[i] : 0) << 22 | (unsigned)dz << 16 | (unsigned)(dy & 0xFF) << 8 | (unsigned)(dx & 0xFF);
     }
-    hipError_t e = hipSuccess;
-#define VER_GEMM_TAPS(L)                                                                                                  \
-    do {                                                                                                                  \
-        e = hipFuncSetAttribute((const void*)k_gemm_nn<L>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);       \
-        if (e == hipSuccess) hipLaunchKernelGGL(k_gemm_nn<L>, dim3((unsigned)(8 * p.per_xcd)), dim3(512), kLdsBytes, st, p); \
-    } while (0)
-    if (layout == 0) VER_GEMM_TAPS(0);
-    else if (layout == 2) VER_GEMM_TAPS(2);
-    else VER_GEMM_TAPS(3);
-#undef VER_GEMM_TAPS
-    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_gemm_nn_taps: LDS attribute: %s", hipGetErrorString(e));
+    const auto kern = layout == 0 ? k_gemm_nn<0> : layout == 2 ? k_gemm_nn<2> : k_gemm_nn<3>;
+    if (int rc = launch_tile_kernel("ver_gemm_nn_taps", kern, p, 8 * p.per_xcd, kLdsBytes, st)) return rc;
     return ver_check_launch("ver_gemm_nn_taps");
 }

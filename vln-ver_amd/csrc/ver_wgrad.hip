@@ -8,14 +8,15 @@
 // answers with depth-32 macro-tiles (0.35-0.43 of the bf16 peak).  Here:
 //   * rows are streamed in slabs of 16 straight into LDS by LDS-DMA (buffer_load_dwordx4 ... lds): a wave instruction
 //     moves 8 rows x 128 B, i.e. whole 128-byte lines of the source;
-//   * the MFMA is v_mfma_f32_16x16x32_bf16 (kShape; the v_mfma_f32_32x32x16_bf16 form, one slab per k-step, is the
-//     body's other value: 2.8 % slower on N(0,1) operands): a k-step spans the slab PAIR 2p, 2p + 1 --
-//     k-groups 0-1 (lanes 0-31) are rows 0-7 / 8-15 of the first slab, k-groups 2-3 of the second.  An odd slab count is
-//     rounded up: rows past M read as zeros (buffer range; implicit A: an offset outside every range);
+//   * the MFMA is v_mfma_f32_16x16x32_bf16: a k-step spans the slab PAIR 2p, 2p + 1 -- k-groups 0-1 (lanes 0-31) are rows
+//     0-7 / 8-15 of the first slab, k-groups 2-3 of the second.  An odd slab count is rounded up: rows past M read as
+//     zeros (buffer range; implicit A: an offset outside every range).  (The body this kernel was first written on, one
+//     slab per k-step of the other bf16 MFMA shape, was 2.8 % slower -- DESIGN.md 3.3 -- and lies in
+//     scratch/experiments/k_wgrad_tn_mfma32.hip.inc);
 //   * the MFMA fragments (8 consecutive k of ONE column per lane) come out of that row-major image through
-//     ds_read_b64_tr_b16, two per fragment; the 16-byte chunks of a 128-byte line are XOR-ed on the SOURCE address (the
-//     LDS-DMA destination is lane-linear) by bit 1 of the row and, in rows 8-15 of a slab, by the 32-byte pair -- the two
-//     16-lane groups of a half read the same columns of rows 0-7 and 8-15 -- which makes every transposing read conflict free;
+//     ds_read_b64_tr_b16, two per fragment; the 16-byte chunks of a 128-byte line are XOR-ed on the SOURCE address so that
+//     every transposing read is conflict free (Shape::swz, ver_gemm_tile.h, which also holds what else this file shares
+//     with ver_gemm.hip: the fragment reads, the lattice addressing and the launchers' common steps);
 //   * a workgroup of 8 waves (2 x 4, wave tile 128 x 64 = 8 x 4 MFMA tiles, 128 accumulator registers) owns a
 //     256 x 256 output tile of one row chunk; the two wave groups (wr = 0 / 1, one wave of each per SIMD) run
 //     half a phase apart: while one issues its 24 fragment reads + 4 LDS-DMA pieces of the slab pair two phases ahead,
@@ -23,63 +24,18 @@
 //   * split over row chunks: block b runs on XCD b % 8 and XCD x works on chunks x, x + 8, ...: the rows of a chunk are
 //     fetched into ONE L2, where the ~32 tiles of the XCD that are in flight share them; fp32 partial tiles go to a
 //     workspace and k_wgrad_reduce adds them up in fp32 (no bf16 rounding of partial sums).
-#include "ver_common.h"
+#include "ver_gemm_tile.h"
 
 namespace {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) void lds_void;
+using namespace gemm_tile;
 
-constexpr int kTile = 256;                  // output tile edge
-constexpr int kSlabRows = 16;               // rows per slab: the k of one 32x32x16 MFMA, half the k of a 16x16x32
+constexpr int kSlabRows = 16;               // rows per slab: half the k of one MFMA
 constexpr int kSlabBytes = 2 * kSlabRows * kTile * 2;   // A part + G part
 constexpr int kRing = 8;
 constexpr int kLdsBytes = kRing * kSlabBytes;           // 128 KiB
-
-typedef int i32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-// MFMA shape of the body (compile time, as in ver_gemm.hip): 32 = v_mfma_f32_32x32x16_bf16, one slab of 16 rows per k-step,
-// 4 x 2 tiles per wave; 16 = v_mfma_f32_16x16x32_bf16, a k-step spans the slab PAIR 2p, 2p + 1 (k-groups 0-1 from the first,
-// 2-3 from the second), 8 x 4 tiles per wave -- phases of two slabs (KP == 2) only.
-constexpr int kShape = 16;
-template <int SH>
-struct Shape {
-    typedef f32x16 acc_t;
-    static constexpr int NI = 4, NJ = 2, NR = 16, TW = 32;
-    // accumulator register r of a lane: row reg_row(r) + lane_row(lane) of the tile, column lane & (TW - 1)
-    static __device__ __forceinline__ int reg_row(int r) { return (r & 3) + 8 * (r >> 2); }
-    static __device__ __forceinline__ int lane_row(int lane) { return 4 * (lane >> 5); }
-    // source-side swizzle of a piece (8 rows x 128 B): position p of row `row` of row group `rowhalf` holds chunk p ^ swz
-    static __device__ __forceinline__ int swz(int row, int rowhalf) { return ((row >> 1) & 1) << 2; }
-};
-template <>
-struct Shape<16> {
-    typedef f32x4 acc_t;
-    static constexpr int NI = 8, NJ = 4, NR = 4, TW = 16;
-    static __device__ __forceinline__ int reg_row(int r) { return r; }
-    static __device__ __forceinline__ int lane_row(int lane) { return 4 * (lane >> 4); }
-    // the two 16-lane groups of a half read the SAME 16 columns of rows 0-7 and 8-15 of a slab (k-groups g, g + 1), 4 KiB
-    // apart: rows 8-15 swap their 32-byte column pairs and the half covers all 64 banks
-    static __device__ __forceinline__ int swz(int row, int rowhalf) { return (((row >> 1) & 1) << 2) ^ (rowhalf << 1); }
-};
-
-// ds_read_b64_tr_b16 as inline asm: behind the builtin the compiler waits for vmcnt(0) in front of every LDS read
-// that follows an LDS-DMA (it cannot tell the ring slots apart), which would serialise the whole pipeline.  The
-// results are only valid behind the s_waitcnt lgkmcnt(0) of phase() (the compiler does not count these reads).
-template <int OFF>
-__device__ __forceinline__ i32x2 tr_read(int addr) {
-    i32x2 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-__device__ __forceinline__ bf16x8 frag(i32x2 lo, i32x2 hi) {
-    return __builtin_bit_cast(bf16x8, (i32x4)__builtin_shufflevector(lo, hi, 0, 1, 2, 3));
-}
+constexpr int kPhaseSlabs = 2;              // slabs per phase: the pair of one k-step
+constexpr int kAhead = 4;                   // prefetch distance in slabs: a pair is requested two phases ahead, like ver_gemm.hip's
+static_assert(kAhead >= kPhaseSlabs && kAhead + 4 <= kRing, "prefetch distance against the ring (WAR on the slot)");
 
 struct WgradArgs {
     const __bf16* A;
@@ -100,21 +56,6 @@ struct WgradArgs {
     signed char kind[64], dz[64], dy[64], dx[64];
 };
 
-constexpr int kOutsideW = (int)0x80000000;
-template <int L>
-__device__ __forceinline__ int wcell_off(const WgradArgs& t, int b, int zl, int y, int x, int dz) {
-    if ((unsigned)y >= (unsigned)t.H || (unsigned)x >= (unsigned)t.W) return kOutsideW;
-    const int j = dz >> 1;
-    int v;
-    if (L == 0)
-        v = ((b * 4 + zl + dz) * t.H + y) * t.W + x;
-    else if (L == 2)
-        v = ((((b * 2 + zl) * t.H + y) * t.W + x) << 1) + j;
-    else
-        v = (((((((y & 1) << 1 | (x & 1)) * t.B + b) * 2 + zl) * (t.H >> 1) + (y >> 1)) * (t.W >> 1) + (x >> 1)) << 1) + j;
-    return v * t.C * 2;
-}
-
 struct WTapLane {       // implicit A: the lane's running row of the DMA stream, addressed through its wave's offset table
     int taddr;                  // LDS byte address of table[pos] for the row AFTER the ones already looked up
     int boff;                   // b * (bytes per viewpoint) + the lane's byte offset inside the segment's vector
@@ -128,17 +69,17 @@ struct WTapLane {       // implicit A: the lane's running row of the DMA stream,
 
 // The wave's offset table (one per 64-column block of the tile, 4 per workgroup, behind the ring in LDS): entry pos = byte
 // offset of the segment's vector for the row at position pos of viewpoint 0 (tap: the neighbouring cell's channel vector, or
-// kOutsideW outside the lattice; pattern block: its row of the pattern table).  A row's source is then ONE LDS read + one add
+// kOutside outside the lattice; pattern block: its row of the pattern table).  A row's source is then ONE LDS read + one add
 // per slab: the per-slab decode (two quotients, the layout's index arithmetic, the bounds checks -- ~40 VALU instructions in
 // front of every 8 MFMAs) cost 20 ms of the 192-viewpoint step.
 template <int L>
 __device__ __forceinline__ int wtap_table_entry(const WgradArgs& t, int seg, int pos) {
-    if (seg < 0) return kOutsideW;                           // (columns past Ka: nothing to read)
+    if (seg < 0) return kOutside;                           // (columns past Ka: nothing to read)
     if (t.kind[seg]) return (pos * t.ncst + t.dz[seg]) * t.CW * 2;
     const int hw = t.H * t.W;
     const int zl = pos / hw, rem = pos - zl * hw;
     const int y = rem / t.W, x = rem - y * t.W;
-    return wcell_off<L>(t, 0, zl, y + t.dy[seg], x + t.dx[seg], t.dz[seg]);
+    return cell_off<L>(LatticeGeom{t.B, t.H, t.W, t.C}, 0, zl, y + t.dy[seg], x + t.dx[seg], t.dz[seg]);
 }
 
 __device__ __forceinline__ int lds_read_b32(int addr) {
@@ -153,7 +94,7 @@ __device__ __forceinline__ int lds_read_b32(int addr) {
 __device__ __forceinline__ void wtap_step(const WgradArgs& t, WTapLane& tl, int tfetched) {
     tl.boff += tl.pend;                                     // (the fetched entry's row may belong to the next viewpoint)
     tl.rows_left -= kSlabRows;
-    tl.vo = tl.rows_left > 0 ? (int)((unsigned)tfetched + (unsigned)tl.boff) : kOutsideW;
+    tl.vo = tl.rows_left > 0 ? (int)((unsigned)tfetched + (unsigned)tl.boff) : kOutside;
     tl.taddr += 4 * kSlabRows;
     tl.pend = 0;
     if (tl.taddr >= tl.tend) tl.taddr -= 4 * t.P, tl.pend = tl.bstep;
@@ -164,10 +105,10 @@ __device__ __forceinline__ void wtap_step(const WgradArgs& t, WTapLane& tl, int 
 __device__ __forceinline__ void wtap_step2(const WgradArgs& t, WTapLane& tl, int tfetched0, int tfetched1) {
     tl.boff += tl.pend;
     tl.rows_left -= kSlabRows;
-    tl.vo = tl.rows_left > 0 ? (int)((unsigned)tfetched0 + (unsigned)tl.boff) : kOutsideW;
+    tl.vo = tl.rows_left > 0 ? (int)((unsigned)tfetched0 + (unsigned)tl.boff) : kOutside;
     tl.boff += tl.pend1;
     tl.rows_left -= kSlabRows;
-    tl.vo1 = tl.rows_left > 0 ? (int)((unsigned)tfetched1 + (unsigned)tl.boff) : kOutsideW;
+    tl.vo1 = tl.rows_left > 0 ? (int)((unsigned)tfetched1 + (unsigned)tl.boff) : kOutside;
     tl.taddr = tl.taddr1 + 4 * kSlabRows;
     tl.pend = 0;
     if (tl.taddr >= tl.tend) tl.taddr -= 4 * t.P, tl.pend = tl.bstep;
@@ -177,42 +118,21 @@ __device__ __forceinline__ void wtap_step2(const WgradArgs& t, WTapLane& tl, int
 }
 
 struct WgradLane {          // per-lane constants of the main loop
-    // LDS byte addresses of the fragment reads in ring slot 0 -- 32x32x16: [0], [1] = column tiles 0 / 1 of a 64-column block;
-    // 16x16x32: the four 16-column tiles of a block, in the lane's slab of the pair and row half
+    // LDS byte addresses of the fragment reads in ring slot 0: the four 16-column tiles of a 64-column block, in the lane's
+    // slab of the pair and row half
     int offA[4], offB[4];
     int voA, voG;                       // per-lane source offsets of the two LDS-DMA pieces this wave moves
     int stepA, stepG;                   // bytes per slab of the sources
     int dmaoff;                         // offset of this wave's piece inside the A / G part of a slab
 };
 
-// Fragments of ring slot SLOT -> registers (12 transposing reads: A tiles 0..3, G tiles 0..1, lo and hi k halves).
-template <int SLOT>
-__device__ __forceinline__ void read_slab(const WgradLane& c, i32x2 (&al)[4], i32x2 (&ah)[4], i32x2 (&bl)[2], i32x2 (&bh)[2]) {
-    // (the offset field of a DS instruction has 16 bits: slots 4-7 go through base registers 64 KiB up)
-    constexpr int SB = (SLOT & 3) * kSlabBytes;
-    constexpr int UP = SLOT >= 4 ? 65536 : 0;
-    const int a0 = c.offA[0] + UP, a1 = c.offA[1] + UP, b0 = c.offB[0] + UP, b1 = c.offB[1] + UP;
-    al[0] = tr_read<SB>(a0);
-    ah[0] = tr_read<SB + 512>(a0);
-    bl[0] = tr_read<SB>(b0);
-    bh[0] = tr_read<SB + 512>(b0);
-    al[1] = tr_read<SB>(a1);
-    ah[1] = tr_read<SB + 512>(a1);
-    bl[1] = tr_read<SB>(b1);
-    bh[1] = tr_read<SB + 512>(b1);
-    al[2] = tr_read<SB + 1024>(a0);
-    ah[2] = tr_read<SB + 1536>(a0);
-    al[3] = tr_read<SB + 1024>(a1);
-    ah[3] = tr_read<SB + 1536>(a1);
-}
-
-// 16x16x32: one phase = the slab pair in ring slots 2 PS, 2 PS + 1 = ONE k-step.  The 16-lane group g of a wave reads rows
+// One phase = the slab pair in ring slots 2 PS, 2 PS + 1 = ONE k-step.  The 16-lane group g of a wave reads rows
 // 8 (g & 1) .. + 7 of slab g >> 1 (both in its base addresses): 8 A tiles + 4 G tiles of 16 columns, two transposing reads
-// each -- the 24 reads of two 32x32x16 slabs; then the LDS-DMA of the pair PF slabs ahead and 32 MFMAs.
-template <int PS, int KP, int PF, int IMPL>
+// each; then the LDS-DMA of the pair kAhead slabs ahead and 32 MFMAs.
+template <int PS, int IMPL>
 __device__ __forceinline__ void phase(char* lds, f32x4 (&acc)[8][4], const WgradLane& c, __amdgpu_buffer_rsrc_t ra,
                                       __amdgpu_buffer_rsrc_t rg, unsigned& soA, unsigned& soG, const WgradArgs& t, WTapLane& tl) {
-    static_assert(KP == 2, "16x16x32: a k-step is a slab pair");
+    // (the offset field of a DS instruction has 16 bits: slots 4-7 go through base registers 64 KiB up)
     constexpr int SB = ((2 * PS) & 3) * kSlabBytes;
     constexpr int UP = 2 * PS >= 4 ? 65536 : 0;
     i32x2 al[8], ah[8], bl[4], bh[4];
@@ -229,7 +149,7 @@ __device__ __forceinline__ void phase(char* lds, f32x4 (&acc)[8][4], const Wgrad
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-        const int ds = (2 * PS + u + PF) % kRing;
+        const int ds = (2 * PS + u + kAhead) % kRing;
         if constexpr (IMPL < 0) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(lds + ds * kSlabBytes + c.dmaoff), 16, c.voA, (int)soA, 0, 0);
         } else {
@@ -241,8 +161,11 @@ __device__ __forceinline__ void phase(char* lds, f32x4 (&acc)[8][4], const Wgrad
         soA += (unsigned)c.stepA;
         soG += (unsigned)c.stepG;
     }
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (PF - KP)) : "memory");
+    // this wave's pieces of the NEXT phase's slabs have landed (everything younger stays in flight)
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (kAhead - kPhaseSlabs)) : "memory");
     __builtin_amdgcn_s_barrier();
+    // the fragment halves pass through the wait as operands: whatever the compiler does to them (copies into the
+    // MFMA's register tuples) is ordered behind it
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(al[0]), "+v"(ah[0]), "+v"(al[1]), "+v"(ah[1]), "+v"(al[2]), "+v"(ah[2]), "+v"(al[3]), "+v"(ah[3]), "+v"(al[4]),
                    "+v"(ah[4]), "+v"(al[5]), "+v"(ah[5]), "+v"(al[6]), "+v"(ah[6]), "+v"(al[7]), "+v"(ah[7]), "+v"(bl[0]), "+v"(bh[0]),
@@ -270,89 +193,21 @@ __device__ __forceinline__ void phase(char* lds, f32x4 (&acc)[8][4], const Wgrad
     __builtin_amdgcn_s_barrier();
 }
 
-// 32x32x16: one phase = KP slabs (ring slots PS*KP ..): fragments -> registers, LDS-DMA of the slabs PF ahead, 8 KP MFMAs.
-template <int PS, int KP, int PF, int IMPL>
-__device__ __forceinline__ void phase(char* lds, f32x16 (&acc)[4][2], const WgradLane& c, __amdgpu_buffer_rsrc_t ra,
-                                      __amdgpu_buffer_rsrc_t rg, unsigned& soA, unsigned& soG, const WgradArgs& t, WTapLane& tl) {
-    i32x2 al[KP][4], ah[KP][4], bl[KP][2], bh[KP][2];
-    int tnext = 0;
-    read_slab<PS * KP>(c, al[0], ah[0], bl[0], bh[0]);
-    if constexpr (KP == 2) read_slab<PS * KP + 1>(c, al[KP - 1], ah[KP - 1], bl[KP - 1], bh[KP - 1]);
-#pragma unroll
-    for (int u = 0; u < KP; ++u) {
-        const int ds = (PS * KP + u + PF) % kRing;
-        if constexpr (IMPL < 0) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(lds + ds * kSlabBytes + c.dmaoff), 16, c.voA, (int)soA, 0, 0);
-        } else {
-            static_assert(IMPL < 0 || KP == 1, "implicit A: one slab per phase");
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(lds + ds * kSlabBytes + c.dmaoff), 16, tl.vo, 0, 0, 0);
-            tnext = lds_read_b32(tl.taddr);                // the entry of the row after (consumed in this phase's MFMA shadow)
-        }
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rg, (lds_void*)(lds + ds * kSlabBytes + kSlabBytes / 2 + c.dmaoff), 16, c.voG, (int)soG, 0, 0);
-        soA += (unsigned)c.stepA;
-        soG += (unsigned)c.stepG;
-    }
-    // this wave's pieces of the NEXT phase's slabs have landed (everything younger stays in flight)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (PF - KP)) : "memory");
-    __builtin_amdgcn_s_barrier();
-    // the fragment halves pass through the wait as operands: whatever the compiler does to them (copies into the
-    // MFMA's register tuples) is ordered behind it
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(al[0][0]), "+v"(ah[0][0]), "+v"(al[0][1]), "+v"(ah[0][1]), "+v"(al[0][2]), "+v"(ah[0][2]), "+v"(al[0][3]),
-                   "+v"(ah[0][3]), "+v"(bl[0][0]), "+v"(bh[0][0]), "+v"(bl[0][1]), "+v"(bh[0][1]), "+v"(tnext)
-                 :
-                 : "memory");
-
-    if constexpr (KP == 2)
-        asm volatile(""
-                     : "+v"(al[KP - 1][0]), "+v"(ah[KP - 1][0]), "+v"(al[KP - 1][1]), "+v"(ah[KP - 1][1]), "+v"(al[KP - 1][2]),
-                       "+v"(ah[KP - 1][2]), "+v"(al[KP - 1][3]), "+v"(ah[KP - 1][3]), "+v"(bl[KP - 1][0]), "+v"(bh[KP - 1][0]),
-                       "+v"(bl[KP - 1][1]), "+v"(bh[KP - 1][1])
-                     :
-                     : "memory");
-    bf16x8 a[KP][4], b[KP][2];
-#pragma unroll
-    for (int u = 0; u < KP; ++u) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) a[u][i] = frag(al[u][i], ah[u][i]);
-        b[u][0] = frag(bl[u][0], bh[u][0]);
-        b[u][1] = frag(bl[u][1], bh[u][1]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int u = 0; u < KP; ++u)
-#pragma unroll
-        for (int it = 0; it < 4; ++it)
-#pragma unroll
-            for (int jt = 0; jt < 2; ++jt)
-                acc[it][jt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[u][it], b[u][jt], acc[it][jt], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (IMPL >= 0) {
-        wtap_step(t, tl, tnext);                            // (a dozen VALU instructions under the MFMAs just issued)
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    __builtin_amdgcn_s_barrier();
-}
-
-template <int PS, int KP, int PF, int IMPL, typename ACC>
-__device__ __forceinline__ void phases_from(int left, char* lds, ACC& acc, const WgradLane& c,
+// phases PS .. of one turn of the ring while slabs are `left`
+template <int PS, int IMPL>
+__device__ __forceinline__ void phases_from(int left, char* lds, f32x4 (&acc)[8][4], const WgradLane& c,
                                             __amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rg, unsigned& soA, unsigned& soG,
                                             const WgradArgs& t, WTapLane& tl) {
-    if constexpr (PS < kRing / KP) {
-        if (left > PS * KP) {
-            phase<PS, KP, PF, IMPL>(lds, acc, c, ra, rg, soA, soG, t, tl);
-            phases_from<PS + 1, KP, PF, IMPL>(left, lds, acc, c, ra, rg, soA, soG, t, tl);
+    if constexpr (PS < kRing / kPhaseSlabs) {
+        if (left > PS * kPhaseSlabs) {
+            phase<PS, IMPL>(lds, acc, c, ra, rg, soA, soG, t, tl);
+            phases_from<PS + 1, IMPL>(left, lds, acc, c, ra, rg, soA, soG, t, tl);
         }
     }
 }
 
-template <int SH, int KP, int PF, int IMPL>
+template <int IMPL>
 __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
-    typedef Shape<SH> sh;
-    static_assert(PF >= KP && PF + (KP == 1 ? 2 : 4) <= kRing, "prefetch distance against the ring (WAR on the slot)");
-    static_assert(SH == 32 || KP == 2, "16x16x32: a k-step is a slab pair");
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -372,8 +227,8 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
     const int mt = tile / p.tiles_n, nt = tile - mt * p.tiles_n;
     const long row0 = (long)chunk * p.Mc;
     const long rows = max(0L, min(p.Mc, p.M - row0));
-    // whole phases; rows past M read as zeros (buffer range), and Mc is a multiple of 16 KP
-    const int nslab = (int)((rows + kSlabRows * KP - 1) / (kSlabRows * KP)) * KP;
+    // whole phases; rows past M read as zeros (buffer range), and Mc is a multiple of a phase's 32 rows
+    const int nslab = (int)((rows + kSlabRows * kPhaseSlabs - 1) / (kSlabRows * kPhaseSlabs)) * kPhaseSlabs;
 
     // LDS-DMA: wave w moves piece (row group w >> 2, 64-column block w & 3) of the A part and of the G part
     const __bf16* ab = IMPL < 0 ? p.A + row0 * p.lda + (long)mt * kTile : nullptr;
@@ -384,7 +239,7 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
     const long gbytes = ((p.M - row0 - 1) * p.ldg + p.N - (long)nt * kTile) * 2;
     const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)gb, 0, (int)max(0L, min(gbytes, 0xFFFFFFFFL)), 0x00020000);
     WgradLane c;
-    const int prow = lane >> 3, pch = (lane & 7) ^ sh::swz(prow, wave >> 2);
+    const int prow = lane >> 3, pch = (lane & 7) ^ Shape::swz(prow, wave >> 2);
     // implicit A: the segment of this wave's 64 columns (boundaries are multiples of 64) -> its source (lattice or pattern
     // table) and tap; the lane's first row
     WTapLane tl = {};
@@ -432,43 +287,32 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
     c.dmaoff = wave * 1024;
     unsigned soA = 0, soG = 0;          // (byte offsets of the running slab: up to 4 GiB, unsigned arithmetic)
 
-    // transposing fragment reads: 16-lane group q = (k half, column half), lane c of it addresses row c >> 2,
-    // columns 4 (c & 3) .. + 3 and receives column c of the group's 4 x 16 block
-    if constexpr (SH == 32) {
-        const int q = lane >> 4, cl = lane & 15;
-        const int lowch = (2 * (q & 1) + ((cl & 3) >> 1)) ^ sh::swz(cl >> 2, q >> 1);
-        const int lbase = (int)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
-        const int rowoff = lbase + ((q >> 1) * 32 + (cl >> 2)) * 128 + lowch * 16 + (cl & 1) * 8;
-        c.offA[0] = rowoff + 2 * wr * 1024;
-        c.offA[1] = c.offA[0] ^ 64;
-        c.offB[0] = rowoff + wc * 1024 + kSlabBytes / 2;
-        c.offB[1] = c.offB[0] ^ 64;
-        c.offA[2] = c.offA[3] = c.offB[2] = c.offB[3] = 0;
-    } else {
-        // 16x16x32: 16-lane group g = k-group: rows 8 (g & 1) .. + 7 (piece row group g & 1, 4 KiB up) of slab g >> 1 of the
-        // pair; lane c of it addresses row c >> 2 (and + 4), chunk 2 t + ((c & 3) >> 1) of column tile t, half c & 1
+    // transposing fragment reads: 16-lane group g = k-group: rows 8 (g & 1) .. + 7 (piece row group g & 1, 4 KiB up) of slab
+    // g >> 1 of the pair; lane c of it addresses row c >> 2 (and + 4), chunk 2 t + ((c & 3) >> 1) of column tile t, half c & 1,
+    // and receives column c of the group's 4 x 16 block
+    {
         const int g = lane >> 4, cl = lane & 15;
         const int lbase = (int)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int ch = (2 * q + ((cl & 3) >> 1)) ^ sh::swz(cl >> 2, g & 1);
+            const int ch = (2 * q + ((cl & 3) >> 1)) ^ Shape::swz(cl >> 2, g & 1);
             const int rowoff = lbase + (g >> 1) * kSlabBytes + (g & 1) * 4096 + (cl >> 2) * 128 + ch * 16 + (cl & 1) * 8;
             c.offA[q] = rowoff + 2 * wr * 1024;
             c.offB[q] = rowoff + wc * 1024 + kSlabBytes / 2;
         }
     }
 
-    typename sh::acc_t acc[sh::NI][sh::NJ];
+    Shape::acc_t acc[Shape::NI][Shape::NJ];
 #pragma unroll
-    for (int it = 0; it < sh::NI; ++it)
+    for (int it = 0; it < Shape::NI; ++it)
 #pragma unroll
-        for (int jt = 0; jt < sh::NJ; ++jt)
+        for (int jt = 0; jt < Shape::NJ; ++jt)
 #pragma unroll
-            for (int r = 0; r < sh::NR; ++r) acc[it][jt][r] = 0.0f;
+            for (int r = 0; r < Shape::NR; ++r) acc[it][jt][r] = 0.0f;
 
-    // prologue: slabs 0 .. PF-1 in flight, the first phase's slabs landed
+    // prologue: slabs 0 .. kAhead - 1 in flight, the first phase's slabs landed
 #pragma unroll
-    for (int s = 0; s < PF; ++s) {
+    for (int s = 0; s < kAhead; ++s) {
         if constexpr (IMPL < 0) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void*)(lds + s * kSlabBytes + c.dmaoff), 16, c.voA, (int)soA, 0, 0);
         } else {
@@ -481,8 +325,8 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
         soA += (unsigned)c.stepA;
         soG += (unsigned)c.stepG;
     }
-    if constexpr (IMPL >= 0 && KP == 2) {
-        // two slabs per phase: tl.vo is slab PF's piece; fetch one more entry for slab PF + 1, then the addresses of the two after
+    if constexpr (IMPL >= 0) {
+        // two slabs per phase: tl.vo is slab kAhead's piece; fetch one more entry for slab kAhead + 1, then the addresses of the two after
         const int vo0 = tl.vo;
         int tn = lds_read_b32(tl.taddr);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tn)::"memory");
@@ -493,30 +337,30 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
         tl.pend1 = 0;
         if (tl.taddr1 >= tl.tend) tl.taddr1 -= 4 * p.P, tl.pend1 = tl.bstep;
     }
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (PF - KP)) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (kAhead - kPhaseSlabs)) : "memory");
     __builtin_amdgcn_s_barrier();
     if (wr == 1) __builtin_amdgcn_s_barrier();          // the second wave group runs half a phase behind
 
     int s = 0;
-    for (; s + kRing <= nslab; s += kRing) phases_from<0, KP, PF, IMPL>(kRing, lds, acc, c, ra, rg, soA, soG, p, tl);
-    phases_from<0, KP, PF, IMPL>(nslab - s, lds, acc, c, ra, rg, soA, soG, p, tl);     // < 8 slabs left: wave-uniform exits
+    for (; s + kRing <= nslab; s += kRing) phases_from<0, IMPL>(kRing, lds, acc, c, ra, rg, soA, soG, p, tl);
+    phases_from<0, IMPL>(nslab - s, lds, acc, c, ra, rg, soA, soG, p, tl);     // < 8 slabs left: wave-uniform exits
     if (wr == 0) __builtin_amdgcn_s_barrier();          // barrier counts of the two groups match again
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the run-ahead pieces nobody reads
 
-    // partial tile -> workspace: register r of tile (it, jt) is row reg_row(r) + lane_row(lane), column lane & (TW - 1) --
-    // 32x32x16: (r & 3) + 8 (r >> 2) + 4 (lane >> 5), lane & 31;  16x16x32: r + 4 (lane >> 4), lane & 15
-    const int i0 = mt * kTile + 128 * wr + sh::lane_row(lane), j0 = nt * kTile + 64 * wc + (lane & (sh::TW - 1));
+    // partial tile -> workspace: register r of tile (it, jt) is row r + 4 (lane >> 4), column lane & 15 of the tile
+    // (Shape::reg_row / lane_row)
+    const int i0 = mt * kTile + 128 * wr + Shape::lane_row(lane), j0 = nt * kTile + 64 * wc + (lane & (Shape::TW - 1));
     if (p.S == 1 && p.out) {
         // one row chunk: there is nothing to add up -- the same fp32 sums, rounded once, straight into the result (a
         // one-viewpoint step has 450 / 1 800 rows: the workspace round trip was 10 of its 12 bytes per element)
 #pragma unroll
-        for (int it = 0; it < sh::NI; ++it)
+        for (int it = 0; it < Shape::NI; ++it)
 #pragma unroll
-            for (int jt = 0; jt < sh::NJ; ++jt) {
-                const int j = j0 + sh::TW * jt;
+            for (int jt = 0; jt < Shape::NJ; ++jt) {
+                const int j = j0 + Shape::TW * jt;
 #pragma unroll
-                for (int r = 0; r < sh::NR; ++r) {
-                    const int i = i0 + sh::TW * it + sh::reg_row(r);
+                for (int r = 0; r < Shape::NR; ++r) {
+                    const int i = i0 + Shape::TW * it + Shape::reg_row(r);
                     if (i < p.Ka && j < p.N) {
                         if (p.out_bf16)
                             reinterpret_cast<__bf16*>(p.out)[(long)i * p.ldo + j] = (__bf16)acc[it][jt][r];
@@ -529,32 +373,26 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& p) {
     }
     float* out = p.ws + (long)chunk * p.Ka * p.N;
 #pragma unroll
-    for (int it = 0; it < sh::NI; ++it)
+    for (int it = 0; it < Shape::NI; ++it)
 #pragma unroll
-        for (int jt = 0; jt < sh::NJ; ++jt) {
-            const int j = j0 + sh::TW * jt;
+        for (int jt = 0; jt < Shape::NJ; ++jt) {
+            const int j = j0 + Shape::TW * jt;
 #pragma unroll
-            for (int r = 0; r < sh::NR; ++r) {
-                const int i = i0 + sh::TW * it + sh::reg_row(r);
+            for (int r = 0; r < Shape::NR; ++r) {
+                const int i = i0 + Shape::TW * it + Shape::reg_row(r);
                 if (i < p.Ka && j < p.N) out[(long)i * p.N + j] = acc[it][jt][r];
             }
         }
 }
 
-// slabs per phase and prefetch distance (in slabs) of the product's shape: 16x16x32 a slab pair, requested two phases ahead
-// like ver_gemm.hip's; 32x32x16 one slab, three ahead (the best of the distances 3-6 and of the pair forms measured in round 5)
-constexpr int kKP = kShape == 16 ? 2 : 1;
-constexpr int kPF = kShape == 16 ? 4 : 3;
-
-template <int SH>
 __global__ __launch_bounds__(512) void k_wgrad_tn(WgradArgs p) {
-    wgrad_body<SH, kKP, kPF, -1>(p);
+    wgrad_body<-1>(p);
 }
 
 // the same kernel with the implicit tap matrix of a lattice in layout L as A (ver_wgrad_tn_segments)
-template <int L, int SH>
+template <int L>
 __global__ __launch_bounds__(512) void k_wgrad_tn_seg(WgradArgs p) {
-    wgrad_body<SH, kKP, kPF, L>(p);
+    wgrad_body<L>(p);
 }
 
 // out[i][j] (bf16 or fp32, row pitch ldo) = sum over the S partial products, fp32; 4 elements per thread
@@ -629,17 +467,46 @@ int pick_splits(long M, int Ka, int N, long ld = 0) {
     return best;
 }
 
-void launch_tn(const WgradArgs& p, int blocks, hipStream_t st, hipError_t& e) {
-    auto kern = k_wgrad_tn<kShape>;
-    e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    if (e == hipSuccess) hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), kLdsBytes, st, p);
-}
-
-template <int L>
-void launch_tn_segments(const WgradArgs& p, int blocks, hipStream_t st, hipError_t& e) {
-    const int ldsb = kLdsBytes + 4 * p.P * 4;            // the ring + four offset tables of P ints
-    e = hipFuncSetAttribute((const void*)k_wgrad_tn_seg<L, kShape>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsb);
-    if (e == hipSuccess) hipLaunchKernelGGL((k_wgrad_tn_seg<L, kShape>), dim3((unsigned)blocks), dim3(512), ldsb, st, p);
+// What ver_wgrad_tn and ver_wgrad_tn_segments (`who`; layout < 0: the explicit operand) do once their operands are checked and
+// p holds them: row chunks, the offset and workspace checks, the launch (or, without rows, zeros) and the reduce.
+int launch_wgrad(const char* who, WgradArgs& p, int layout, long M, long Ka, int N, void* out, long ldo, int out_dtype, int splits,
+                 void* workspace, long workspace_bytes, hipStream_t st) {
+    const long ld = p.lda > p.ldg ? p.lda : p.ldg;
+    const int S = splits > 0 ? splits : pick_splits(M, (int)Ka, N, ld);
+    VER_REQUIRE(S <= 65536, VER_EINVAL, "%s: %d row chunks", who, S);
+    const long Mc = ((M + S - 1) / S + 2 * kSlabRows - 1) / (2 * kSlabRows) * (2 * kSlabRows);  // rows per chunk, whole phases
+    VER_REQUIRE((Mc + 16 * kRing) * ld * 2 < 0xFFFFFFFFL, VER_EUNSUPPORTED,
+                "%s: a row chunk exceeds the 4-GiB range of a buffer offset (more splits)", who);
+    VER_REQUIRE(workspace_bytes >= (long)S * Ka * N * (long)sizeof(float), VER_EINVAL, "%s: workspace of %ld bytes, %ld needed", who,
+                workspace_bytes, (long)S * Ka * N * (long)sizeof(float));
+    p.ws = (float*)workspace;
+    p.M = M;
+    p.Mc = Mc;
+    p.S = S;
+    p.Ka = (int)Ka;
+    p.N = N;
+    p.tiles_n = (N + kTile - 1) / kTile;
+    p.T = (int)((Ka + kTile - 1) / kTile) * p.tiles_n;
+    const bool direct = S == 1 && M > 0;
+    p.out = direct ? out : nullptr;
+    p.ldo = ldo;
+    p.out_bf16 = out_dtype == VER_BF16;
+    if (M > 0) {
+        const auto kern = layout < 0 ? k_wgrad_tn : layout == 0 ? k_wgrad_tn_seg<0> : layout == 2 ? k_wgrad_tn_seg<2> : k_wgrad_tn_seg<3>;
+        const int ldsb = layout < 0 ? kLdsBytes : kLdsBytes + 4 * p.P * 4;      // implicit A: the ring + four offset tables of P ints
+        if (int rc = launch_tile_kernel(who, kern, p, p.T * S, ldsb, st)) return rc;
+    } else if (int zrc = ver_zero_async(workspace, (size_t)S * Ka * N * sizeof(float), st)) {   // (kernel zero fill: ver_zero_async)
+        return zrc;
+    }
+    if (direct) return ver_check_launch(who);
+    const long n4 = Ka * N / 4;
+    long grid = (n4 + 255) / 256;
+    if (grid > 8192) grid = 8192;
+    if (out_dtype == VER_F32)
+        hipLaunchKernelGGL(k_wgrad_reduce<float>, dim3((unsigned)grid), dim3(256), 0, st, (const float*)workspace, (float*)out, ldo, S, (int)Ka, N);
+    else
+        hipLaunchKernelGGL(k_wgrad_reduce<__bf16>, dim3((unsigned)grid), dim3(256), 0, st, (const float*)workspace, (__bf16*)out, ldo, S, (int)Ka, N);
+    return ver_check_launch(who);
 }
 }  // namespace
 
@@ -661,7 +528,6 @@ extern "C" long ver_wgrad_tn_workspace(long M, int Ka, int N, int splits) {
 
 extern "C" int ver_wgrad_tn(const void* a, long lda, const void* g, long ldg, long M, int Ka, int N, void* out, long ldo,
                             int out_dtype, int splits, int flags, void* workspace, long workspace_bytes, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
     VER_REQUIRE(M >= 0 && Ka > 0 && N > 0, VER_EINVAL, "ver_wgrad_tn: bad sizes M=%ld Ka=%d N=%d", M, Ka, N);
     VER_REQUIRE(out && workspace && ((a && g) || M == 0), VER_EINVAL, "ver_wgrad_tn: null pointer argument");
     VER_REQUIRE(out_dtype == VER_F32 || out_dtype == VER_BF16, VER_EINVAL, "ver_wgrad_tn: out_dtype %d", out_dtype);
@@ -671,55 +537,18 @@ extern "C" int ver_wgrad_tn(const void* a, long lda, const void* g, long ldg, lo
                 "ver_wgrad_tn: operands must be 16-byte aligned with row pitches that are multiples of 8 elements");
     VER_REQUIRE(N % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)out & 15) == 0, VER_EUNSUPPORTED,
                 "ver_wgrad_tn: N and the output pitch must be multiples of 4");
-    const int S = splits > 0 ? splits : pick_splits(M, Ka, N, lda > ldg ? lda : ldg);
-    VER_REQUIRE(S <= 65536, VER_EINVAL, "ver_wgrad_tn: %d row chunks", S);
-    const long Mc = ((M + S - 1) / S + 2 * kSlabRows - 1) / (2 * kSlabRows) * (2 * kSlabRows);  // rows per chunk, whole phases
-    VER_REQUIRE((Mc + 16 * kRing) * (lda > ldg ? lda : ldg) * 2 < 0xFFFFFFFFL, VER_EUNSUPPORTED,
-                "ver_wgrad_tn: a row chunk exceeds the 4-GiB range of a buffer offset (more splits)");
-    VER_REQUIRE(workspace_bytes >= (long)S * Ka * N * (long)sizeof(float), VER_EINVAL, "ver_wgrad_tn: workspace of %ld bytes, %ld needed",
-                workspace_bytes, (long)S * Ka * N * (long)sizeof(float));
     WgradArgs p = {};
     p.A = (const __bf16*)a;
     p.G = (const __bf16*)g;
-    p.ws = (float*)workspace;
     p.lda = lda;
     p.ldg = ldg;
-    p.M = M;
-    p.Mc = Mc;
-    p.S = S;
-    p.Ka = Ka;
-    p.N = N;
-    p.tiles_n = (N + kTile - 1) / kTile;
-    p.T = ((Ka + kTile - 1) / kTile) * p.tiles_n;
-    const bool direct = S == 1 && M > 0;
-    p.out = direct ? out : nullptr;
-    p.ldo = ldo;
-    p.out_bf16 = out_dtype == VER_BF16;
-    hipError_t e = hipSuccess;
-    if (M > 0) {
-        launch_tn(p, p.T * S, st, e);
-        if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_wgrad_tn: LDS attribute: %s", hipGetErrorString(e));
-    } else if (int zrc = ver_zero_async(workspace, (size_t)S * Ka * N * sizeof(float), st)) {   // (kernel zero fill: ver_zero_async)
-        return zrc;
-    }
-    if (direct) return ver_check_launch("ver_wgrad_tn");
-    const long n4 = (long)Ka * N / 4;
-    long grid = (n4 + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    if (out_dtype == VER_F32)
-        hipLaunchKernelGGL(k_wgrad_reduce<float>, dim3((unsigned)grid), dim3(256), 0, st, (const float*)workspace, (float*)out, ldo, S, Ka, N);
-    else
-        hipLaunchKernelGGL(k_wgrad_reduce<__bf16>, dim3((unsigned)grid), dim3(256), 0, st, (const float*)workspace, (__bf16*)out, ldo, S, Ka, N);
-    return ver_check_launch("ver_wgrad_tn");
+    return launch_wgrad("ver_wgrad_tn", p, -1, M, Ka, N, out, ldo, out_dtype, splits, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int ver_wgrad_tn_segments(const void* lattice, int layout, int B, int H, int W, int C, const int* taps, int nseg,
                                      const void* cst, int ncst, int cw, const void* g, long ldg, int N, void* out, long ldo,
                                      int out_dtype, int splits, void* workspace, long workspace_bytes, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    VER_REQUIRE(B >= 0 && H > 0 && W > 0 && C > 0 && N > 0 && nseg > 0, VER_EINVAL, "ver_wgrad_tn_segments: bad sizes");
-    VER_REQUIRE(layout == 0 || layout == 2 || layout == 3, VER_EINVAL, "ver_wgrad_tn_segments: layout %d (0 plain, 2 z-split, 3 planar z-split)", layout);
-    VER_REQUIRE(layout != 3 || (H % 2 == 0 && W % 2 == 0), VER_EINVAL, "ver_wgrad_tn_segments: planar needs even H, W");
+    if (int rc = check_lattice_args("ver_wgrad_tn_segments", layout, B, H, W, C, N, nseg)) return rc;
     VER_REQUIRE(out && workspace && ((lattice && g && taps) || B == 0), VER_EINVAL, "ver_wgrad_tn_segments: null pointer argument");
     VER_REQUIRE(out_dtype == VER_F32 || out_dtype == VER_BF16, VER_EINVAL, "ver_wgrad_tn_segments: out_dtype %d", out_dtype);
     VER_REQUIRE(nseg <= 64, VER_EUNSUPPORTED, "ver_wgrad_tn_segments: %d segments (at most 64)", nseg);
@@ -734,70 +563,28 @@ extern "C" int ver_wgrad_tn_segments(const void* lattice, int layout, int B, int
                 "ver_wgrad_tn_segments: g must be 16-byte aligned with a row pitch that is a multiple of 8 elements");
     VER_REQUIRE(N % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)out & 15) == 0, VER_EUNSUPPORTED,
                 "ver_wgrad_tn_segments: N and the output pitch must be multiples of 4");
-    WgradArgs p = {};
     long Ka = 0;
-    for (int i = 0; i < nseg; ++i) {
-        const int dz = taps[3 * i], dy = taps[3 * i + 1], dx = taps[3 * i + 2];
-        p.seg_start[i] = (int)Ka;
-        if (dz < 0) {
-            VER_REQUIRE(cst && -1 - dz < ncst, VER_EINVAL, "ver_wgrad_tn_segments: segment %d names pattern block %d of %d", i, -1 - dz, cst ? ncst : 0);
-            p.kind[i] = 1, p.dz[i] = (signed char)(-1 - dz);
-            Ka += cw;
-        } else {
-            VER_REQUIRE((dz == 0 || dz == 2) && dy >= -64 && dy <= 64 && dx >= -64 && dx <= 64, VER_EINVAL,
-                        "ver_wgrad_tn_segments: tap %d = (%d, %d, %d): dz must be 0 or 2", i, dz, dy, dx);
-            p.kind[i] = 0, p.dz[i] = (signed char)dz, p.dy[i] = (signed char)dy, p.dx[i] = (signed char)dx;
-            Ka += C;
-        }
+    if (int rc = check_segments("ver_wgrad_tn_segments", "ver_wgrad_tn_segments", taps, nseg, C, cst, ncst, cw, &Ka)) return rc;
+    VER_REQUIRE(Ka < 0x7FFFFFFFL, VER_EUNSUPPORTED, "ver_wgrad_tn_segments: %ld columns", Ka);
+    WgradArgs p = {};
+    for (int i = 0, col = 0; i < nseg; ++i) {
+        const int dz = taps[3 * i];
+        p.seg_start[i] = col;
+        p.kind[i] = dz < 0;
+        p.dz[i] = (signed char)(dz < 0 ? -1 - dz : dz);
+        if (dz >= 0) p.dy[i] = (signed char)taps[3 * i + 1], p.dx[i] = (signed char)taps[3 * i + 2];
+        col += dz < 0 ? cw : C;
     }
     p.seg_start[nseg] = (int)Ka;
-    VER_REQUIRE(Ka < 0x7FFFFFFFL, VER_EUNSUPPORTED, "ver_wgrad_tn_segments: %ld columns", Ka);
-    const int S = splits > 0 ? splits : pick_splits(M, (int)Ka, N, ldg);
-    VER_REQUIRE(S <= 65536, VER_EINVAL, "ver_wgrad_tn_segments: %d row chunks", S);
-    const long Mc = ((M + S - 1) / S + 2 * kSlabRows - 1) / (2 * kSlabRows) * (2 * kSlabRows);
-    VER_REQUIRE((Mc + 16 * kRing) * ldg * 2 < 0xFFFFFFFFL, VER_EUNSUPPORTED,
-                "ver_wgrad_tn_segments: a row chunk exceeds the 4-GiB range of a buffer offset (more splits)");
-    VER_REQUIRE(workspace_bytes >= (long)S * Ka * N * (long)sizeof(float), VER_EINVAL, "ver_wgrad_tn_segments: workspace of %ld bytes, %ld needed",
-                workspace_bytes, (long)S * Ka * N * (long)sizeof(float));
-    p.A = nullptr;
     p.G = (const __bf16*)g;
-    p.ws = (float*)workspace;
-    p.lda = 0;
     p.ldg = ldg;
-    p.M = M;
-    p.Mc = Mc;
-    p.S = S;
-    p.Ka = (int)Ka;
-    p.N = N;
-    p.tiles_n = (N + kTile - 1) / kTile;
-    p.T = (int)((Ka + kTile - 1) / kTile) * p.tiles_n;
-    const bool direct = S == 1 && M > 0;
-    p.out = direct ? out : nullptr;
-    p.ldo = ldo;
-    p.out_bf16 = out_dtype == VER_BF16;
     p.lattice = (const __bf16*)lattice;
     p.lattice_bytes = lbytes;
     p.cst = (const __bf16*)cst;
     p.cst_bytes = cst ? (long)P * ncst * cw * 2 : 0;
     p.B = B, p.H = H, p.W = W, p.C = C, p.P = P, p.CW = cw, p.ncst = ncst, p.nseg = nseg;
-    hipError_t e = hipSuccess;
-    if (M > 0) {
-        if (layout == 0) launch_tn_segments<0>(p, p.T * S, st, e);
-        else if (layout == 2) launch_tn_segments<2>(p, p.T * S, st, e);
-        else launch_tn_segments<3>(p, p.T * S, st, e);
-        if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_wgrad_tn_segments: LDS attribute: %s", hipGetErrorString(e));
-    } else if (int zrc = ver_zero_async(workspace, (size_t)S * Ka * N * sizeof(float), st)) {   // (kernel zero fill: ver_zero_async)
-        return zrc;
-    }
-    if (direct) return ver_check_launch("ver_wgrad_tn_segments");
-    const long n4 = Ka * N / 4;
-    long grid = (n4 + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    if (out_dtype == VER_F32)
-        hipLaunchKernelGGL(k_wgrad_reduce<float>, dim3((unsigned)grid), dim3(256), 0, st, (const float*)workspace, (float*)out, ldo, S, (int)Ka, N);
-    else
-        hipLaunchKernelGGL(k_wgrad_reduce<__bf16>, dim3((unsigned)grid), dim3(256), 0, st, (const float*)workspace, (__bf16*)out, ldo, S, (int)Ka, N);
-    return ver_check_launch("ver_wgrad_tn_segments");
+    return launch_wgrad("ver_wgrad_tn_segments", p, layout, M, Ka, N, out, ldo, out_dtype, splits, workspace, workspace_bytes,
+                        (hipStream_t)stream);
 }
 
 extern "C" int ver_wgrad_tn_segments_splits(int B, int H, int W, long Ka, int N, long ldg) {

@@ -2182,28 +2182,16 @@ def gemm_nn_taps(lattice, layout, combined_hw, taps, w, rowpos=None, bias=None, 
     ``planes`` = list with the source plane of every tap: ``lattice`` is then [planes, ...] -- several lattices of one shape
     (the four class planes of a layer's output gradient), tap t reads ``lattice[planes[t]]``."""
     lat, w = _gpu(lattice, 'lattice'), _gpu(w, 'w')
-    H, W = combined_hw
     plane_elems = nplanes = 0
     if planes is not None:
         nplanes, plane_elems = int(lat.shape[0]), int(lat[0].numel())
         if len(planes) != len(taps) or not lat.is_contiguous():
             raise ValueError('gemm_nn_taps: one source plane per tap, contiguous planes')
-        B, _, C = _lattice_dims(lat[0], int(layout))
-        lat_one = lat[0]
-    else:
-        B, _, C = _lattice_dims(lat, int(layout))
-        lat_one = lat
+    lat_one = lat[0] if planes is not None else lat
+    B, H, W, C, const_rows, ncst, cw, kdim, arr, ntaps = _segment_args(lat_one, layout, combined_hw, taps, const_rows, 'gemm_nn_taps')
     if not gemm_nn_taps_supported(lat_one, int(layout), w, C):
         raise RuntimeError('gemm_nn_taps: unsupported operands %s layout %d / %s %s' % (tuple(lat.shape), layout, tuple(w.shape), w.stride()))
     m, n = B * 2 * H * W, w.shape[1]
-    ncst = cw = 0
-    if const_rows is not None:
-        const_rows = _gpu(const_rows, 'const_rows')
-        if not (const_rows.is_contiguous() and const_rows.dtype == torch.bfloat16 and const_rows.dim() == 3 and const_rows.shape[0] == 2 * H * W):
-            raise ValueError('gemm_nn_taps: const_rows must be a contiguous bf16 [2 H W, blocks, width] table')
-        ncst, cw = int(const_rows.shape[1]), int(const_rows.shape[2])
-    taps = [((-1 - int(t[1]), 0, 0) if t[0] == 'c' else t) for t in taps]
-    kdim = sum(cw if t[0] < 0 else C for t in taps)
     if w.shape[0] != kdim:
         raise ValueError('gemm_nn_taps: w has %d rows, the segments span %d columns' % (w.shape[0], kdim))
     if out is None:
@@ -2216,11 +2204,9 @@ def gemm_nn_taps(lattice, layout, combined_hw, taps, w, rowpos=None, bias=None, 
             raise ValueError('gemm_nn_taps: rowpos must be [2 H W, N]')
     if bias is not None:
         bias = _gpu(bias, 'bias').float().contiguous()
-    flat = [int(v) for t in taps for v in t]
-    arr = (ctypes.c_int * len(flat))(*flat)
-    parr = (ctypes.c_int * len(taps))(*[int(v) for v in planes]) if planes is not None else None
+    parr = (ctypes.c_int * ntaps)(*[int(v) for v in planes]) if planes is not None else None
     _launch(timer_class, lambda: lib().ver_gemm_nn_planes(
-        _p(lat), layout, B, H, W, C, plane_elems, nplanes, parr, arr, len(taps), _p(const_rows), ncst, cw, _p(w), w.stride(0),
+        _p(lat), layout, B, H, W, C, plane_elems, nplanes, parr, arr, ntaps, _p(const_rows), ncst, cw, _p(w), w.stride(0),
         _p(rowpos), _p(bias), _p(out), out.stride(0), n, _stream()), meta=dict(flops=2.0 * m * w.shape[0] * n))
     return out
 
