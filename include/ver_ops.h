@@ -427,13 +427,13 @@ int ver_run_scatter(const void* rows, void* image, long image_stride, const int3
  *             (ver_occ_mlp_image_bytes() bytes, 16-byte aligned): MFMA weight fragments
  *   vectors : f32 [ver_occ_mlp_vector_floats()] = b1 gamma1 beta1 b2 gamma2 beta2 (128 each) b3 (16)
  *   forward : x bf16 [N,128] -> logits bf16 [N,16]
- *   first_linear = 0: the first Linear has been folded into the producer of x (two Linears in a row compose:
+ *   flags   : bit 0 = first Linear.  Clear: the first Linear has been folded into the producer of x (two Linears in a row compose:
  *             `occ_proj` :571 feeds `occ_branches[0]` :580 with nothing in between), x is ITS output and the chain
  *             starts at the first LayerNorm; W1 / b1 of image / vectors are ignored, grad_a1 may be NULL,
  *             grad_x = d loss / d x is then the gradient w.r.t. that output, and no dW1 is to be formed.
- *   ver_occ_mlp_forward takes `first_linear` as FLAGS: bit 0 as above, bit 1 = VER_OCC_MLP_CENTERED: the caller has
+ *             Bit 1 = VER_OCC_MLP_CENTERED: the caller has
  *             centred the weights and biases of both hidden Linears over their OUTPUT axis (W <- W - mean_o W,
- *             b <- b - mean b; with first_linear = 0 the centring of Linear 1 sits in the producer of x), so every
+ *             b <- b - mean b; with bit 0 clear the centring of Linear 1 sits in the producer of x), so every
  *             LayerNorm input has zero row mean and the kernel skips the mean pass.  LayerNorm is invariant to a
  *             per-row constant: LN(Wx + b) = LN(PWx + Pb), P = I - 11^T/128 -- the same function of the parameters;
  *             the caller maps the gradients of the centred parameters back through P (autograd does).
@@ -443,14 +443,14 @@ long ver_occ_mlp_image_bytes(void);
 int ver_occ_mlp_vector_floats(void);
 int ver_occ_mlp_pack(const float* W1, const float* W2, const float* W3, void* image, void* stream);
 int ver_occ_mlp_forward(const void* x, const void* image, const float* vectors, void* logits,
-                        long N, int width, int classes, float eps, int first_linear, void* stream);
+                        long N, int width, int classes, float eps, int flags, void* stream);
 /*   the same, also writing the reciprocal standard deviation of both LayerNorms per row (ABI 24):
  *     rstd f32 [N, 2]  (may be NULL: plain forward).  ver_occ_mlp_backward_fused_stats reads it back, so that its two
  *     recomputed LayerNorm-forward steps need no statistics (elementwise; VER_OCC_MLP_CENTERED rows only).
  */
 int ver_occ_mlp_forward_stats(const void* x, const void* image, const float* vectors, void* logits, float* rstd,
-                              long N, int width, int classes, float eps, int first_linear, void* stream);
-/*   backward: re-computes the forward from x, then
+                              long N, int width, int classes, float eps, int flags, void* stream);
+/*   backward (first_linear: zero or not, as bit 0 of the forward's flags; no centred form): re-computes the forward from x, then
  *     grad_x  bf16 [N,128]                      d loss / d x
  *     grad_a1, grad_a2 bf16 [N,128]             gradients w.r.t. the outputs of Linear 1 / Linear 2
  *     h1      bf16 [N,128]                      input of Linear 2 (post-ReLU activation)
@@ -531,7 +531,7 @@ int  ver_occ_confusion(const void* logits, int dtype, long rows_per_sample, int 
 /* ---------------------------------------------------------------------------------------
  * The same two results WITHOUT the logits: the classification runs in the epilogue of the fused MLP forward kernel
  * (csrc/ver_occ_mlp.hip), on the bf16 logits ver_occ_mlp_forward would have stored -- they never reach memory.
- *   x, image, vectors, width, classes, eps, flags: as ver_occ_mlp_forward (flags bit 0 = first_linear, bit 1 =
+ *   x, image, vectors, width, classes, eps, flags: as ver_occ_mlp_forward (flags bit 0 = first Linear, bit 1 =
  *               VER_OCC_MLP_CENTERED; x and image 16-byte aligned; another width / class count: VER_EUNSUPPORTED)
  * ver_occ_mlp_confusion: labels, rows_per_sample, samples, thresholds (HOST array, copied into the kernel arguments: a
  *   captured launch keeps them), num_thresholds (1 to 8) and hist (8-byte aligned, ACCUMULATED, never cleared) as

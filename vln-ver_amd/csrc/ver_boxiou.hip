@@ -253,9 +253,7 @@ extern "C" int ver_det_match(const float* pred_boxes, const int32_t* pred_labels
     const size_t lds = (size_t)Pcap * pitch * sizeof(float) + (size_t)(Pcap + Gcap) * (sizeof(BoxTerms) + sizeof(int)) +
                        (size_t)Pcap * 4 * sizeof(int);
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_det_match), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_det_match: LDS attribute: %s", hipGetErrorString(e));
+        if (int rc = ver_lds_limit("ver_det_match", reinterpret_cast<const void*>(k_det_match), lds)) return rc;
     }
     hipLaunchKernelGGL(k_det_match, dim3((unsigned)S), dim3(kBoxThreads), lds, (hipStream_t)stream, pred_boxes, pred_labels,
                        pred_scores, pred_valid, gt_boxes, gt_labels, ngt, thr, num_thresholds, iou_max, gt_index, tp_bits,

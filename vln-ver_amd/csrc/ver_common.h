@@ -20,6 +20,22 @@ int ver_zero_async(void* ptr, size_t bytes, void* stream);
         if (!(cond)) return ver_fail(code, __VA_ARGS__); \
     } while (0)
 
+// Raise a kernel's dynamic-LDS limit to `lds` bytes: a launch that asks for more than the 64 KiB default needs it first.  (The
+// attribute is per device: it is set on every call -- a host-side table write.)
+inline int ver_lds_limit(const char* who, const void* kern, size_t lds) {
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "%s: LDS attribute: %s", who, hipGetErrorString(e));
+    return VER_OK;
+}
+
+// set the kernel's dynamic-LDS limit, launch it, check the launch
+template <typename K, typename... Args>
+int launch_lds(const char* who, K kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    if (int rc = ver_lds_limit(who, reinterpret_cast<const void*>(kern), lds)) return rc;
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    return ver_check_launch(who);
+}
+
 // Bilinear footprint of one sample on an H x W map, mmcv / Deformable-DETR convention
 // (SURVEY.md A.3): pixel coords x = loc_x*W - 0.5, y = loc_y*H - 0.5; the sample contributes
 // only if -1 < x < W and -1 < y < H; corners outside [0,W-1]x[0,H-1] contribute zero.

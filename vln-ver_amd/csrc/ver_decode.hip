@@ -134,9 +134,7 @@ extern "C" int ver_det_decode(const void* cls, int cls_dtype, const float* box, 
     if (threads > kDecodeThreads) threads = kDecodeThreads;
     const size_t lds = cls ? (size_t)n * sizeof(unsigned long long) : 0;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_det_decode), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_det_decode: LDS attribute: %s", hipGetErrorString(e));
+        if (int rc = ver_lds_limit("ver_det_decode", reinterpret_cast<const void*>(k_det_decode), lds)) return rc;
     }
     hipLaunchKernelGGL(k_det_decode, dim3((unsigned)B), dim3((unsigned)threads), lds, (hipStream_t)stream, cls,
                        cls_dtype == VER_BF16 ? 1 : 0, box, box_ld, out_boxes, out_scores, out_labels, out_valid, out_query, rng,

@@ -118,8 +118,7 @@ inline int check_segments(const char* who, const char* who_tap, const int* taps,
 // attribute first).  The caller picks the instantiation and checks the launch.
 template <typename Args>
 int launch_tile_kernel(const char* who, void (*kern)(Args), const Args& p, int blocks, int lds_bytes, hipStream_t st) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "%s: LDS attribute: %s", who, hipGetErrorString(e));
+    if (int rc = ver_lds_limit(who, (const void*)kern, lds_bytes)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds_bytes, st, p);
     return VER_OK;
 }

@@ -497,10 +497,7 @@ int check_mha(const char* who, bool all_pointers, const int64_t* seed, int dtype
 }
 
 int grow_lds(const char* who, const void* kern, size_t lds) {
-    if (lds <= 64 * 1024) return VER_OK;
-    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "%s: LDS attribute: %s", who, hipGetErrorString(e));
-    return VER_OK;
+    return lds <= 64 * 1024 ? VER_OK : ver_lds_limit(who, kern, lds);
 }
 }  // namespace
 

@@ -121,12 +121,11 @@ __global__ __launch_bounds__(256) void k_occ_mlp_pack(const float* __restrict__ 
 // ----------------------------------------------------------------------------------------- forward
 namespace {
 // LayerNorm + ReLU of one row tile held transposed: acc[ot][i] = feature 16ot + 4g + i of row c.
-// Returns the B fragments of the next layer (k-step t <- tiles 2t, 2t+1); optionally the normalised
-// values (for the backward pass).
+// Returns the B fragments of the next layer (k-step t <- tiles 2t, 2t+1).
 // CENTERED: the caller guarantees rows with zero mean over the 128 features (the weights / bias of the producing Linear were
 // centred over their OUTPUT axis, W <- W - mean_o W, b <- b - mean(b): LayerNorm is invariant to a per-row constant, so
 // LN(Wx + b) = LN(PWx + Pb) with P = I - 11^T/128) -- the mean pass and its two cross-lane reductions drop out.
-template <bool KEEP, bool CENTERED = false>
+template <bool CENTERED>
 __device__ __forceinline__ void ln_relu_tile(f32x4 (&acc)[8], const float* gam, const float* bet, float eps,
                                              bf16x8 (&out)[4], float& rstd_out) {   // gam/bet already offset by 4g
     // (measured and dropped: starting the MFMA chains from 0 and adding the bias here -- the compiler ties vdst to src C,
@@ -157,8 +156,7 @@ __device__ __forceinline__ void ln_relu_tile(f32x4 (&acc)[8], const float* gam, 
             const int ot = 2 * t + h;
             const f32x4 gm = *reinterpret_cast<const f32x4*>(gam + 16 * ot);
             const f32x4 bt = *reinterpret_cast<const f32x4*>(bet + 16 * ot);
-            if (KEEP) acc[ot] *= rs;                       // normalised value stays in acc
-            y[h] = KEEP ? acc[ot] * gm + bt : acc[ot] * (gm * rs) + bt;
+            y[h] = acc[ot] * (gm * rs) + bt;
         }
         out[t] = relu_packed(pack8(y[0], y[1]));
     }
@@ -168,7 +166,7 @@ __device__ __forceinline__ void ln_relu_tile(f32x4 (&acc)[8], const float* gam, 
 namespace {
 // The same on a row tile in the NATURAL fragment layout (what a 16-byte load of x gives: lane (row c, g) holds features
 // 32t + 8g + j of the row in x[t][j]).  Used when the first Linear has been folded into the producer of x
-// (first_linear = 0): x is the pre-LayerNorm activation itself.  gam / bet already offset by 8g.
+// (flags bit 0 clear): x is the pre-LayerNorm activation itself.  gam / bet already offset by 8g.
 // KEEP: also return the normalised values (bf16) and form the output from those rounded values (backward pass).
 // QUAD: the four lanes that share a row are a quad (lane = 4 row + chunk) instead of the same column of the four 16-lane rows
 // (lane = row + 16 chunk): the row statistics are then two DPP quad permutes instead of two ds_bpermute round trips.
@@ -278,9 +276,9 @@ __device__ __forceinline__ void classify_tile(f32x4 acc, int lane, int& best, fl
 // Confusion mode deals the rows PER SAMPLE: workgroup (bx, s) owns rows [bx, bx + 1) * kEpiChunkRows of sample s and nothing
 // else, so no block straddles two samples and the histogram is flushed once, at the end.  A workgroup counts at most
 // kEpiChunkRows < 2^16 rows: its bins are 16 bits wide, two to an LDS word (a 32-bit add of 1 << 16 * (bin & 1) cannot
-// carry), [8, 17, 17] bins in 4 624 B instead of 9 248 -- with all 68 fragments (first_linear = 1) that is 77 392 B per
-// workgroup and two workgroups still share a CU's 160 KB.  With first_linear = 0 section kF2 is never read: those
-// instantiations stage 36 fragments (layer 3 moves up to fragment 32), 44 624 B.
+// carry), [8, 17, 17] bins in 4 624 B instead of 9 248 -- with all 68 fragments (L1) that is 77 392 B per
+// workgroup and two workgroups still share a CU's 160 KB.  With the first Linear folded away section kF2 is never read: those
+// instantiations stage 36 fragments (layer 3 moves up to fragment 32), 44 624 B (fwd_lds_bytes).
 constexpr int kEpiLogits = 0, kEpiConfusion = 1, kEpiClasses = 2;
 constexpr int kEpiMaxT = 8;
 constexpr int kEpiK = kC + 1;
@@ -304,19 +302,29 @@ struct FwdEpilogue<kEpiClasses> {
     float thr;
 };
 
-// L1 = false (first_linear = 0, ver_ops.h): x is the output of the first Linear already.  The chain starts with the first
+constexpr int kFwdRT = 4;       // 16-row tiles a wave takes through the chain together: 64-row blocks
+// Fragments a forward instantiation stages, and its dynamic LDS: the classifying instantiations of the folded chain stage only
+// the sections it reads, kF1 and kF3; the vectors follow the fragments, confusion mode's bins the vectors.
+constexpr bool fwd_compact(bool l1, int epi) { return epi != kEpiLogits && !l1; }
+constexpr int fwd_staged_frags(bool l1, int epi) { return fwd_compact(l1, epi) ? kF2 + (kFwdFrags - kF3) : kFwdFrags; }
+constexpr size_t fwd_lds_bytes(bool l1, int epi) {
+    return (size_t)fwd_staged_frags(l1, epi) * 1024 + kVecFloats * sizeof(float) +
+           (epi == kEpiConfusion ? kEpiBinWords * sizeof(unsigned) : 0);
+}
+
+// L1 = false (flags bit 0 clear, ver_ops.h): x is the output of the first Linear already.  The chain starts with the first
 // LayerNorm in the natural fragment layout; the image was packed with W2 in W1's place, so section kF1 holds W2 with the
 // natural k order that layout needs (and kB1, in the backward kernel, W2's dgrad with natural-order output rows).
 // CENTERED (flags bit 1): every LayerNorm input has zero row mean by construction (see ln_relu_tile).
 // STATS: also write 1/std of both LayerNorms per row (rstd f32 [N, 2]; 32-bit buffer addressing: N < 2^28 rows).
-template <int RT, bool L1, bool CENTERED = false, bool STATS = false, int EPI = kEpiLogits>
+template <bool L1, bool CENTERED, bool STATS, int EPI>
 __global__ __launch_bounds__(256, 2) void k_occ_mlp_fwd(const __bf16* __restrict__ x, const __bf16* __restrict__ img,
                                                         const float* __restrict__ vec, __bf16* __restrict__ logits,
                                                         long N, float eps, float* __restrict__ rstd, FwdEpilogue<EPI> ep) {
+    constexpr int RT = kFwdRT;
     static_assert(EPI == kEpiLogits || (RT == 4 && !STATS), "the classifying epilogues keep one row per lane: 64-row blocks");
-    // the classifying instantiations of the folded chain stage only the sections it reads: kF1 and kF3
-    constexpr bool kCompact = EPI != kEpiLogits && !L1;
-    constexpr int kStaged = kCompact ? kF2 + (kFwdFrags - kF3) : kFwdFrags, kL3 = kCompact ? kF2 : kF3;
+    constexpr bool kCompact = fwd_compact(L1, EPI);
+    constexpr int kStaged = fwd_staged_frags(L1, EPI), kL3 = kCompact ? kF2 : kF3;    // (compact: layer 3 moves up to fragment 32)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     bf16x8* frag = reinterpret_cast<bf16x8*>(smem);                       // [kStaged][64]
     float* sv = reinterpret_cast<float*>(smem + kStaged * 1024);          // vectors
@@ -408,7 +416,7 @@ __global__ __launch_bounds__(256, 2) void k_occ_mlp_fwd(const __bf16* __restrict
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 float rs;
-                ln_relu_tile<false, CENTERED>(acc[rt], bias + kW, bias + 2 * kW, eps, bf[rt], rs);
+                ln_relu_tile<CENTERED>(acc[rt], bias + kW, bias + 2 * kW, eps, bf[rt], rs);
                 if constexpr (STATS)
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, rs), rs_rsrc,
                                                           g == 0 ? (int)(r0 + rt * 16 + c) * 8 + 4 * layer : -8, 0, 0);
@@ -619,10 +627,7 @@ __device__ __forceinline__ void ln_relu_bwd(f32x4 (&d)[8], const bf16x8 (&xh)[4]
 // holds feature kperm(t, g, j) (16-byte stores); the caller un-permutes the small weight gradients.
 // L1 = false: see k_occ_mlp_fwd.  h1 is then stored in NATURAL feature order and grad_x is the gradient w.r.t. the
 // kernel's input = the folded Linear's output; grad_a1 is not written.
-#ifndef VER_MLP_BWD_WAVES
-#define VER_MLP_BWD_WAVES 4
-#endif
-constexpr int kBwdWaves = VER_MLP_BWD_WAVES;       // waves per workgroup (one workgroup per CU: the image fills the LDS)
+constexpr int kBwdWaves = 4;       // waves per workgroup: one per SIMD, for the registers (one workgroup per CU: the image fills the LDS)
 template <bool L1>
 __global__ __launch_bounds__(kBwdWaves * 64) void k_occ_mlp_bwd(const __bf16* __restrict__ x, const __bf16* __restrict__ dlog,
                                                         const __bf16* __restrict__ img, const float* __restrict__ vec,
@@ -821,58 +826,58 @@ extern "C" int ver_occ_mlp_pack(const float* W1, const float* W2, const float* W
     return ver_check_launch("ver_occ_mlp_pack");
 }
 
-extern "C" int ver_occ_mlp_forward(const void* x, const void* image, const float* vectors, void* logits, long N,
-                                   int width, int classes, float eps, int first_linear, void* stream) {
-    return ver_occ_mlp_forward_stats(x, image, vectors, logits, nullptr, N, width, classes, eps, first_linear, stream);
+namespace {
+// run f with every bool as a std::bool_constant argument: f names the instantiation it launches by `decltype(b)::value`
+template <typename F>
+int dispatch_bools(F&& f) {
+    return f();
+}
+template <typename F, typename... Rest>
+int dispatch_bools(F&& f, bool b, Rest... rest) {
+    auto with = [&](auto c) { return dispatch_bools([&](auto... cs) { return f(c, cs...); }, rest...); };
+    return b ? with(std::true_type{}) : with(std::false_type{});
 }
 
+// The forward kernel: flags (bit 0 = first Linear, bit 1 = VER_OCC_MLP_CENTERED), rstd -> k_occ_mlp_fwd<L1, CENTERED, STATS, EPI>.
+// The classifying epilogues (ver_occ_mlp_confusion / ver_occ_mlp_classes) store neither logits nor statistics.
+template <int EPI>
+int launch_fwd(const char* who, const void* x, const void* image, const float* vectors, void* logits, float* rstd, long N,
+               float eps, int flags, dim3 grid, FwdEpilogue<EPI> ep, void* stream) {
+    return dispatch_bools(
+        [&](auto l1, auto centered, auto stats) {
+            constexpr bool L1 = decltype(l1)::value, CENTERED = decltype(centered)::value;
+            constexpr bool STATS = EPI == kEpiLogits && decltype(stats)::value;
+            return launch_lds(who, k_occ_mlp_fwd<L1, CENTERED, STATS, EPI>, grid, dim3(256), fwd_lds_bytes(L1, EPI),
+                              (hipStream_t)stream, (const __bf16*)x, (const __bf16*)image, vectors, (__bf16*)logits, N, eps, rstd, ep);
+        },
+        flags & 1, flags & 2, rstd != nullptr);
+}
+}  // namespace
+
+extern "C" int ver_occ_mlp_forward(const void* x, const void* image, const float* vectors, void* logits, long N,
+                                   int width, int classes, float eps, int flags, void* stream) {
+    return ver_occ_mlp_forward_stats(x, image, vectors, logits, nullptr, N, width, classes, eps, flags, stream);
+}
+
+// flags: bit 0 = the chain starts with Linear 1 (clear: folded into the producer of x); bit 1 (VER_OCC_MLP_CENTERED) = every
+// LayerNorm input has zero row mean by construction, the mean pass is skipped
 extern "C" int ver_occ_mlp_forward_stats(const void* x, const void* image, const float* vectors, void* logits, float* rstd,
-                                         long N, int width, int classes, float eps, int first_linear, void* stream) {
+                                         long N, int width, int classes, float eps, int flags, void* stream) {
     int rc = check_common("ver_occ_mlp_forward", x, image, vectors, N, width, classes);
     if (rc) return rc;
     if (N == 0) return VER_OK;
     VER_REQUIRE(logits, VER_EINVAL, "ver_occ_mlp_forward: null logits pointer");
-    constexpr int RT = 4;
-    const size_t lds = (size_t)kFwdFrags * 1024 + kVecFloats * sizeof(float);
-    // (the attribute is per device: set it on every call, as ver_sca does -- it is a host-side table write)
-    // first_linear: bit 0 = the chain starts with Linear 1 (0: folded into the producer of x); bit 1 (VER_OCC_MLP_CENTERED)
-    // = every LayerNorm input has zero row mean by construction, the mean pass is skipped
-    VER_REQUIRE((first_linear & ~3) == 0, VER_EINVAL, "ver_occ_mlp_forward: unknown flags 0x%x", first_linear);
-    const bool l1 = first_linear & 1, centered = first_linear & 2;
+    VER_REQUIRE((flags & ~3) == 0, VER_EINVAL, "ver_occ_mlp_forward: unknown flags 0x%x", flags);
     VER_REQUIRE(!rstd || (N < (1L << 28) && ((uintptr_t)rstd & 7) == 0), VER_EUNSUPPORTED,
                 "ver_occ_mlp_forward_stats: rstd needs N < 2^28 rows and 8-byte alignment");
-    auto kern = l1 ? (centered ? (rstd ? k_occ_mlp_fwd<RT, true, true, true> : k_occ_mlp_fwd<RT, true, true, false>)
-                               : (rstd ? k_occ_mlp_fwd<RT, true, false, true> : k_occ_mlp_fwd<RT, true, false, false>))
-                   : (centered ? (rstd ? k_occ_mlp_fwd<RT, false, true, true> : k_occ_mlp_fwd<RT, false, true, false>)
-                               : (rstd ? k_occ_mlp_fwd<RT, false, false, true> : k_occ_mlp_fwd<RT, false, false, false>));
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_occ_mlp_forward: LDS attribute: %s", hipGetErrorString(e));
-    const long nblk = (N + 16 * RT - 1) / (16 * RT);
+    const long nblk = (N + 16 * kFwdRT - 1) / (16 * kFwdRT);
     long grid = (nblk + 3) / 4;
     if (grid > 512) grid = 512;                            // 2 workgroups per CU, persistent
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, (const __bf16*)x,
-                       (const __bf16*)image, vectors, (__bf16*)logits, N, eps, rstd, FwdEpilogue<kEpiLogits>{});
-    return ver_check_launch("ver_occ_mlp_forward");
+    return launch_fwd("ver_occ_mlp_forward", x, image, vectors, logits, rstd, N, eps, flags, dim3((unsigned)grid),
+                      FwdEpilogue<kEpiLogits>{}, stream);
 }
 
 // ---- classification inside the forward kernel (ver_occ_mlp_confusion / ver_occ_mlp_classes) ---------------------------
-namespace {
-template <int EPI>
-int launch_fwd_epilogue(const char* who, const void* x, const void* image, const float* vectors, long N, float eps, int flags,
-                        dim3 grid, FwdEpilogue<EPI> ep, void* stream) {
-    const bool l1 = flags & 1, centered = flags & 2;
-    auto kern = l1 ? (centered ? k_occ_mlp_fwd<4, true, true, false, EPI> : k_occ_mlp_fwd<4, true, false, false, EPI>)
-                   : (centered ? k_occ_mlp_fwd<4, false, true, false, EPI> : k_occ_mlp_fwd<4, false, false, false, EPI>);
-    const size_t lds = (size_t)(l1 ? kFwdFrags : kF2 + (kFwdFrags - kF3)) * 1024 + kVecFloats * sizeof(float) +
-                       (EPI == kEpiConfusion ? kEpiBinWords * sizeof(unsigned) : 0);
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "%s: LDS attribute: %s", who, hipGetErrorString(e));
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, (hipStream_t)stream, (const __bf16*)x, (const __bf16*)image, vectors,
-                       (__bf16*)nullptr, N, eps, (float*)nullptr, ep);
-    return ver_check_launch(who);
-}
-}  // namespace
-
 extern "C" int ver_occ_mlp_confusion(const void* x, const void* image, const float* vectors, const uint8_t* labels,
                                      long rows_per_sample, int samples, const float* thresholds, int num_thresholds,
                                      int64_t* hist, int width, int classes, float eps, int flags, void* stream) {
@@ -898,8 +903,8 @@ extern "C" int ver_occ_mlp_confusion(const void* x, const void* image, const flo
     ep.hist = reinterpret_cast<unsigned long long*>(hist);
     for (int t = 0; t < num_thresholds; ++t) ep.thr[t] = thresholds[t];
     ep.T = num_thresholds;
-    return launch_fwd_epilogue<kEpiConfusion>(who, x, image, vectors, rows_per_sample, eps, flags,
-                                              dim3((unsigned)chunks, (unsigned)samples), ep, stream);
+    return launch_fwd(who, x, image, vectors, nullptr, nullptr, rows_per_sample, eps, flags,
+                      dim3((unsigned)chunks, (unsigned)samples), ep, stream);
 }
 
 extern "C" int ver_occ_mlp_classes(const void* x, const void* image, const float* vectors, uint8_t* cls, float* prob, long N,
@@ -917,7 +922,7 @@ extern "C" int ver_occ_mlp_classes(const void* x, const void* image, const float
     FwdEpilogue<kEpiClasses> ep = {cls, prob, threshold};
     long grid = (N + 255) / 256;
     if (grid > 512) grid = 512;                            // 2 workgroups per CU, persistent (as ver_occ_mlp_forward)
-    return launch_fwd_epilogue<kEpiClasses>(who, x, image, vectors, N, eps, flags, dim3((unsigned)grid), ep, stream);
+    return launch_fwd(who, x, image, vectors, nullptr, nullptr, N, eps, flags, dim3((unsigned)grid), ep, stream);
 }
 
 extern "C" int ver_occ_mlp_backward(const void* x, const void* grad_logits, const void* image, const float* vectors,
@@ -928,22 +933,16 @@ extern "C" int ver_occ_mlp_backward(const void* x, const void* grad_logits, cons
     VER_REQUIRE(param_grads, VER_EINVAL, "ver_occ_mlp_backward: null parameter-gradient pointer");
     hipStream_t st = (hipStream_t)stream;
     if (int zrc = ver_zero_async(param_grads, (6 * kW + kC * kW + kC) * sizeof(float), st)) return zrc;   // (kernel: ver_zero_async)
-    hipError_t e = hipSuccess;
-    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_occ_mlp_backward: memset: %s", hipGetErrorString(e));
     if (N == 0) return VER_OK;
     VER_REQUIRE(grad_logits && grad_x && (grad_a1 || !first_linear) && grad_a2 && h1, VER_EINVAL,
                 "ver_occ_mlp_backward: null pointer argument");
     const size_t lds = (size_t)kAllFrags * 1024 + kVecFloats * sizeof(float);
-    auto kern = first_linear ? k_occ_mlp_bwd<true> : k_occ_mlp_bwd<false>;
-    e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "ver_occ_mlp_backward: LDS attribute: %s", hipGetErrorString(e));
     const long nblk = (N + 15) / 16;
     long grid = (nblk + kBwdWaves - 1) / kBwdWaves;
     if (grid > 256) grid = 256;                            // one workgroup per CU (LDS bound), persistent
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBwdWaves * 64), lds, st, (const __bf16*)x,
-                       (const __bf16*)grad_logits, (const __bf16*)image, vectors, (__bf16*)grad_x, (__bf16*)grad_a1,
-                       (__bf16*)grad_a2, (__bf16*)h1, param_grads, N, eps);
-    return ver_check_launch("ver_occ_mlp_backward");
+    return launch_lds("ver_occ_mlp_backward", first_linear ? k_occ_mlp_bwd<true> : k_occ_mlp_bwd<false>, dim3((unsigned)grid),
+                      dim3(kBwdWaves * 64), lds, st, (const __bf16*)x, (const __bf16*)grad_logits, (const __bf16*)image, vectors,
+                      (__bf16*)grad_x, (__bf16*)grad_a1, (__bf16*)grad_a2, (__bf16*)h1, param_grads, N, eps);
 }
 
 // ============================================================================================
@@ -1038,7 +1037,8 @@ __device__ __forceinline__ void ns_ln_relu_bwd(f32x4 (&d)[8], const bf16x8 (&xh)
 //     rows     A.0    B.6    A.2    B.0    A.4    B.2    A.6    B.4
 //     features B.5    A.1    B.7    A.3    B.1    A.5    B.3    A.7
 // Steps of a block: 0 LN1 fwd | 1 a2 = W2 h1 | 2 LN2 fwd | 3 d(h2), d(W3) | 4 LN2 bwd | 5 LN2 sums, d(h1) | 6 LN1 bwd |
-// 7 LN1 sums, d(W2), store d(x)  (d(W2) in step 5 with -DVER_WS_DW2_STEP7=0: the same time on the box that measured both).
+// 7 LN1 sums, d(W2), store d(x)  (d(W2) in step 5 instead: the same time on the box that measured both;
+// scratch/experiments/k_occ_mlp_bwd_ws_dw2_step5.hip.inc).
 // LDS: per block set T0 h1, T1 a2 -> d(h2) -> n2 -> n1, T2 h2 -> d(z2) -> d(z1), T3 d(a2), DL; ONE shared tile T4 for d(h1),
 // which step 6 turns into d(x) in place (A writes it in slot 5, rewrites it in slot 6, the feature team stores it in slot 7;
 // B in slots 0, 1 and 3): 9 x 17 KB + 4 KB + vectors = 159.6 KB.
@@ -1050,18 +1050,9 @@ __device__ __forceinline__ void ns_ln_relu_bwd(f32x4 (&d)[8], const bf16x8 (&xh)
 // s_waitcnt vmcnt(0) of a round are written where they cost nothing.  29.3 -> 24.8-25.7 ms over 96.8 M rows.
 namespace {
 constexpr int kWsRows = 64;
-#ifndef VER_WS_DW2_STEP7
-#define VER_WS_DW2_STEP7 1
-#endif
-#ifndef VER_WS_AHEAD
-#define VER_WS_AHEAD 2
-#endif
-#ifndef VER_WS_BIAS_LATE
-#define VER_WS_BIAS_LATE 0
-#endif
-constexpr bool kWsBiasLate = VER_WS_BIAS_LATE;         // step 1: b2 added to the finished tile (8 more registers) or the accumulators' start value
-constexpr int kWsAhead = VER_WS_AHEAD;                 // operand fragments requested ahead in the 64-row products of steps 1 and 5
-constexpr bool kWsDw2InStep7 = VER_WS_DW2_STEP7;       // d(W2) in step 7 (beside the row team's heavy LN2 backward) or in step 5
+// Operand fragments requested ahead in the 64-row products of steps 1 and 5.  Measured (round 6, at rows_product): two ahead -- a
+// ring of three -- 23.1 ms against 24.1 with one fragment in flight; a tile's four ahead spill accumulators, 31.4 ms.
+constexpr int kWsAhead = 2;
 constexpr int kWsTile = kWsRows * kNsLd;
 constexpr int kWsVec0 = kW;                                      // b1 is not staged (folded mode)
 constexpr size_t kWsLds = (size_t)9 * kWsTile * 2 + (size_t)2 * kWsRows * kNsDlLd * 2 + (kVecFloats - kWsVec0) * sizeof(float);
@@ -1089,30 +1080,12 @@ __device__ __forceinline__ int ws_tl_probe() { return (blockIdx.x % 29 == 3 && b
         if (pr_ >= 0 && (threadIdx.x & 63) == 0)                                                                    \
             g_ws_tl_span[(pr_ * 8 + (threadIdx.x >> 6)) * 2 + (which)] = (long long)__builtin_amdgcn_s_memtime();   \
     } while (0)
-// (-DVER_WS_TIMELINE_FINE: four more stamps inside the LayerNorm backward of slots 1 and 4; they cost those steps ~600 cycles)
-#ifdef VER_WS_TIMELINE_FINE
-__device__ long long g_ws_tl_fine[kWsTlProbes * 8 * kWsTlRounds * 8];
-#define WS_TLF(k, idx)                                                                                              \
-    do {                                                                                                            \
-        const int pr_ = ws_tl_probe();                                                                              \
-        const long kk_ = (k) - kWsTlFirst;                                                                          \
-        if (pr_ >= 0 && kk_ >= 0 && kk_ < kWsTlRounds && (threadIdx.x & 63) == 0 && (idx) < 8)                      \
-            g_ws_tl_fine[((pr_ * 8 + (threadIdx.x >> 6)) * kWsTlRounds + kk_) * 8 + (idx)] =                        \
-                (long long)__builtin_amdgcn_s_memtime();                                                            \
-    } while (0)
-extern "C" int ver_ws_timeline_fine_read(long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ws_tl_fine), sizeof(long long) * kWsTlProbes * 8 * kWsTlRounds * 8);
-}
-#else
-#define WS_TLF(k, idx) do { } while (0)
-#endif
 extern "C" int ver_ws_timeline_read(long long* slots, long long* span) {
     hipError_t e = hipMemcpyFromSymbol(slots, HIP_SYMBOL(g_ws_tl), sizeof(long long) * kWsTlProbes * 8 * kWsTlRounds * 8 * 2);
     if (e != hipSuccess) return (int)e;
     return (int)hipMemcpyFromSymbol(span, HIP_SYMBOL(g_ws_tl_span), sizeof(long long) * kWsTlProbes * 8 * 2);
 }
 #else
-#define WS_TLF(k, idx) do { } while (0)
 #define WS_TL(k, slot, which) do { } while (0)
 #define WS_SPAN(which) do { } while (0)
 #endif
@@ -1247,12 +1220,8 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
             //     re-packing took 3.5;
             //   * a = (dg - m1 - n m2) rs is evaluated as dg rs + (n k2 + k1) with k1 = -m1 rs, k2 = -m2 rs per row: two fused
             //     multiply-adds per value instead of four operations.
-            long tl_k = 0;
-            int tl_base = 0;
-            (void)tl_k; (void)tl_base;
             auto ln_bwd4 = [&](const bf16x8 (&din)[4], const bf16x8 (&hin)[4], const bf16x8 (&xh)[4], const float (&rs)[4],
                                const f32x4 (&gm)[2], __bf16* pz, __bf16* pn, auto&& put) {
-                WS_TLF(tl_k, tl_base + 0);
                 f32x4 dg[4][2], nn[4][2];
                 float s1[4], s2[4];
 #pragma unroll
@@ -1286,13 +1255,11 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
                     s1[i] = sa1 + sb1;
                     s2[i] = sa2 + sb2;
                 }
-                WS_TLF(tl_k, tl_base + 1);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     s1[i] = group_sum<16>(s1[i]);
                     s2[i] = group_sum<16>(s2[i]);
                 }
-                WS_TLF(tl_k, tl_base + 2);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const float k1 = -(s1[i] * (1.0f / kW)) * rs[i], k2 = -(s2[i] * (1.0f / kW)) * rs[i];
@@ -1306,7 +1273,6 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
                     }
                     put(i, pack8(a[0], a[1]));
                 }
-                WS_TLF(tl_k, tl_base + 3);
             };
             auto r0 = [&](Row4& st, __bf16* T, __bf16* DL) {
                 st.rsv[0] = rsn[0];
@@ -1362,14 +1328,9 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
             for (long k = 0; k < rounds; ++k) {
                 const bool va = 2 * k < nmine, vb = 2 * k + 1 < nmine, vp = k > 0 && 2 * k - 1 < nmine;
                 const long blk_a = blockIdx.x + (2 * k) * (long)gridDim.x, blk_b = blk_a + gridDim.x;
-#ifdef VER_WS_ABL_NOROW
-                for (int sl = 0; sl < 8; ++sl) lds_barrier();
-                continue;
-#endif
                 if (va) r0(sa, TA, DLs);
                 prefetch(blk_b);                                    // B's block of this round: step 0 in slot 3
                 WS_SLOT_END(k, 0);
-                tl_k = k; tl_base = 4;
                 if (vp) r6(sb, TB);
                 WS_SLOT_END(k, 1);
                 if (va) r2(sa, TA);
@@ -1377,9 +1338,7 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
                 if (vb) r0(sb, TB, DLs + kWsRows * kNsDlLd);
                 prefetch(blk_a + 2 * (long)gridDim.x);              // A's block of the next round: step 0 in slot 0
                 WS_SLOT_END(k, 3);
-                tl_base = 0;
                 if (va) r4(sa, TA);
-                tl_base = 8;
                 WS_SLOT_END(k, 4);
                 if (vb) r2(sb, TB);
                 WS_SLOT_END(k, 5);
@@ -1473,10 +1432,6 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
         for (long k = 0; k < rounds; ++k) {
             const bool va = 2 * k < nmine, vb = 2 * k + 1 < nmine, vp = k > 0 && 2 * k - 1 < nmine;
             const long blk_a = blockIdx.x + (2 * k) * (long)gridDim.x, blk_b = blk_a + gridDim.x;
-#ifdef VER_WS_ABL_NOROW
-            (void)blk_a; (void)blk_b; (void)va; (void)vb; (void)vp;
-            for (int sl = 0; sl < 8; ++sl) lds_barrier();
-#else
             if (va) r0(sa, TA, DLs, blk_a);
             lds_barrier();
             if (vp) r6(sb, TB);
@@ -1493,7 +1448,6 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
             lds_barrier();
             if (vb) r4(sb, TB);
             lds_barrier();
-#endif
         }
         return;
     }
@@ -1554,21 +1508,20 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
         for (int i = 0; i < NF; ++i) {
             const int rt = i >> 2, ks = i & 3;
             if (i + kWsAhead < NF) b[(i + kWsAhead) % RING] = frag(i + kWsAhead);
-            // (the bias is ADDED to the finished tile, not the accumulators' start value: requested here it has four k-steps to
-            //  arrive; as the start value every tile began with an exposed LDS round trip)
+            // (the bias is the accumulators' START value.  Added to the finished tile instead it would have four k-steps to arrive,
+            //  but stays live beside them: 8 more registers, part of the full pipeline that spilled --
+            //  scratch/experiments/k_occ_mlp_bwd_ws_bias_late.hip.inc)
             if (ks == 0 && init) {
 #pragma unroll
                 for (int ot = 0; ot < OT; ++ot) bias[ot] = *reinterpret_cast<const f32x4*>(init + 16 * ot);
             }
             __builtin_amdgcn_sched_barrier(0);
-            const bool late = kWsBiasLate || !init;
 #pragma unroll
-            for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma(w[ot][ks], b[i % RING], ks == 0 ? (late ? zero4 : bias[ot]) : acc[ot]);
+            for (int ot = 0; ot < OT; ++ot) acc[ot] = mfma(w[ot][ks], b[i % RING], ks == 0 ? (init ? bias[ot] : zero4) : acc[ot]);
             if (ks == 3) {
 #pragma unroll
                 for (int ot = 0; ot < OT; ++ot)
-                    *reinterpret_cast<bf16x4*>(dst + (16 * rt + c) * kNsLd + f0 + 16 * ot + 4 * g) =
-                        pack4(init && kWsBiasLate ? acc[ot] + bias[ot] : acc[ot]);
+                    *reinterpret_cast<bf16x4*>(dst + (16 * rt + c) * kNsLd + f0 + 16 * ot + 4 * g) = pack4(acc[ot]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -1601,22 +1554,11 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
 #pragma unroll
             for (int ot = 0; ot < OT; ++ot) {
                 ada[ot] = ns_tr_frag(T + 3 * kWsTile, kNsLd, 32 * ks, f0 + 16 * ot, c, g);
-#ifndef VER_WS_ABL_NOSUMS
                 sb2[ot] = mfma(ada[ot], ones, sb2[ot]);
                 const bf16x8 adz = ns_tr_frag(T + 2 * kWsTile, kNsLd, 32 * ks, f0 + 16 * ot, c, g);
                 sbet2[ot] = mfma(adz, ones, sbet2[ot]);
                 // d(gamma2)[f] = sum_r d(z2)[r][f] n2[r][f] = the DIAGONAL of d(z2)^T n2 (T1 holds n2 itself)
                 sgam2[ot] = mfma(adz, ns_tr_frag(T + kWsTile, kNsLd, 32 * ks, f0 + 16 * ot, c, g), sgam2[ot]);
-#endif
-            }
-            if constexpr (!kWsDw2InStep7) {
-#pragma unroll
-                for (int kt = 0; kt < 8; ++kt) {
-                    const bf16x8 b = ns_tr_frag(T, kNsLd, 32 * ks, 16 * kt, c, g);
-#pragma unroll
-                    for (int ot = 0; ot < OT; ++ot) dw2[ot][kt] = mfma(ada[ot], b, dw2[ot][kt]);
-                    if (kt & 1) __builtin_amdgcn_sched_barrier(0);
-                }
             }
         }
         rows_product(T + 3 * kWsTile, T4, wb2, nullptr);
@@ -1630,21 +1572,17 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
             bf16x8 ada[OT];
 #pragma unroll
             for (int ot = 0; ot < OT; ++ot) {
-                if constexpr (kWsDw2InStep7) ada[ot] = ns_tr_frag(T + 3 * kWsTile, kNsLd, 32 * ks, f0 + 16 * ot, c, g);
-#ifndef VER_WS_ABL_NOSUMS
+                ada[ot] = ns_tr_frag(T + 3 * kWsTile, kNsLd, 32 * ks, f0 + 16 * ot, c, g);
                 const bf16x8 adz = ns_tr_frag(T + 2 * kWsTile, kNsLd, 32 * ks, f0 + 16 * ot, c, g);
                 sbet1[ot] = mfma(adz, ones, sbet1[ot]);
                 sgam1[ot] = mfma(adz, ns_tr_frag(T + kWsTile, kNsLd, 32 * ks, f0 + 16 * ot, c, g), sgam1[ot]);      // diagonal, as in step 5
-#endif
             }
-            if constexpr (kWsDw2InStep7) {
 #pragma unroll
-                for (int kt = 0; kt < 8; ++kt) {
-                    const bf16x8 b = ns_tr_frag(T, kNsLd, 32 * ks, 16 * kt, c, g);
+            for (int kt = 0; kt < 8; ++kt) {
+                const bf16x8 b = ns_tr_frag(T, kNsLd, 32 * ks, 16 * kt, c, g);
 #pragma unroll
-                    for (int ot = 0; ot < OT; ++ot) dw2[ot][kt] = mfma(ada[ot], b, dw2[ot][kt]);
-                    if (kt & 1) __builtin_amdgcn_sched_barrier(0);
-                }
+                for (int ot = 0; ot < OT; ++ot) dw2[ot][kt] = mfma(ada[ot], b, dw2[ot][kt]);
+                if (kt & 1) __builtin_amdgcn_sched_barrier(0);
             }
         }
     };
@@ -1673,10 +1611,6 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
         __bf16* const DLB = DLs + kWsRows * kNsDlLd;
         for (long k = 0; k < rounds; ++k) {
             const bool va = 2 * k < nmine, vb = 2 * k + 1 < nmine, vp = k > 0 && 2 * k - 1 < nmine;
-#ifdef VER_WS_ABL_NOFEAT
-            (void)va; (void)vb; (void)vp; (void)DLA; (void)DLB;
-            for (int sl = 0; sl < 8; ++sl) lds_barrier();
-#else
             const long blk_a = blockIdx.x + (2 * k) * (long)gridDim.x;
             if (vp) f5(TB);
             WS_SLOT_END(k, 0);
@@ -1696,7 +1630,6 @@ __global__ __launch_bounds__(512) void k_occ_mlp_bwd_ws(const __bf16* __restrict
             if (va) f7(TA);
             if (va) store_dx(blk_a);                          // A's d(x): in T4 since slot 6, T4 is rewritten in slot 0
             WS_SLOT_END(k, 7);
-#endif
         }
     }
     WS_SPAN(1);
@@ -1782,12 +1715,9 @@ static int occ_mlp_backward_fused(const char* who, const void* x, const void* gr
     const bool use_rstd = rstd && (flags & VER_OCC_MLP_CENTERED);
     auto kern = (flags & VER_OCC_MLP_CENTERED) ? (use_rstd ? k_occ_mlp_bwd_ws<true, true> : k_occ_mlp_bwd_ws<true, false>)
                                                : k_occ_mlp_bwd_ws<false, false>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWsLds);
-    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "%s: LDS attribute: %s", who, hipGetErrorString(e));
-    hipLaunchKernelGGL(kern, dim3((unsigned)gridw), dim3(512), kWsLds, st, (const __bf16*)x, (const __bf16*)grad_logits, W2,
-                       W3, vectors, (__bf16*)grad_x, slabbed ? slabs : param_grads, N, eps, grad_scale,
-                       use_rstd ? rstd : nullptr, slabbed ? (long)kPgradFloats : 0L);
-    int rc = ver_check_launch(who);
+    int rc = launch_lds(who, kern, dim3((unsigned)gridw), dim3(512), kWsLds, st, (const __bf16*)x, (const __bf16*)grad_logits, W2,
+                        W3, vectors, (__bf16*)grad_x, slabbed ? slabs : param_grads, N, eps, grad_scale,
+                        use_rstd ? rstd : nullptr, slabbed ? (long)kPgradFloats : 0L);
     if (rc || !slabbed) return rc;
     hipLaunchKernelGGL(k_pgrad_reduce, dim3((kPgradFloats + 255) / 256), dim3(256), 0, st, slabs, (int)gridw, param_grads);
     return ver_check_launch(who);

@@ -1942,16 +1942,6 @@ size_t sca_bwd_mm_lds(int head_dim, int map_h, int map_w) {
     return (mt <= 16 && slack_ok && tile_b + ds_b + g_b <= kMaxLds) ? tile_b + ds_b + g_b : 0;
 }
 
-// set the kernel's dynamic-LDS limit, launch it, check the launch
-template <typename K, typename... Args>
-int launch_lds(const char* what, K kern, unsigned blocks, int threads, size_t lds, hipStream_t st, Args... args) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return ver_fail(VER_ELAUNCH, "%s: LDS attribute: %s", what, hipGetErrorString(e));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, st, args...);
-    return ver_check_launch(what);
-}
-
 template <typename F>
 int dispatch_shape(int hd, int points, F&& f) {
 #define VER_CASE(HD_, G_)                                                                              \
