@@ -915,7 +915,8 @@ def test_occ_mlp_fused_forward():
 
 def test_occ_mlp_fused_backward():
     """ver_occ_mlp_backward (re-computed chain + dgrad chain in registers, row-reduced weight
-    gradients) vs autograd through the fp64 reference on the same bf16-rounded operands."""
+    gradients) vs autograd through the fp64 reference on the same bf16-rounded operands.
+    The per-feature check of these kernels, on gate-stable rows, is test_occ_mlp_gates_gpu.py."""
     hip = pkg('hipops')
     gen = torch.Generator(device='cpu').manual_seed(12)
     p = _occ_mlp_params(gen)
@@ -948,7 +949,8 @@ def test_occ_mlp_fused_with_folded_first_linear(fused, monkeypatch):
     ``fused``: the wave-specialised N-split backward kernel that accumulates d(W2) itself (ver_occ_mlp_backward_fused, the
     default) / the row-split kernel + host GEMM over its side tensors.
     x := bf16(Linear1(x0)); forward and every gradient (d x = gradient w.r.t. that output) vs autograd through the
-    fp64 chain LayerNorm -> ReLU -> Linear2 -> LayerNorm -> ReLU -> Linear3 on the same x."""
+    fp64 chain LayerNorm -> ReLU -> Linear2 -> LayerNorm -> ReLU -> Linear3 on the same x.
+    The per-feature check of these kernels, on gate-stable rows, is test_occ_mlp_gates_gpu.py."""
     hip = pkg('hipops')
     monkeypatch.setattr(hip, '_OCC_MLP_BWD_FUSED', fused)
     gen = torch.Generator(device='cpu').manual_seed(13)
@@ -1030,7 +1032,8 @@ def test_occ_mlp_centered_equals_plain_and_the_fp64_chain():
     (W <- W - mean_o W, b <- b - mean b) every LayerNorm input has zero row mean and the kernels skip the mean pass.
     LayerNorm is invariant to a per-row constant, so this is the SAME function of the parameters: forward and every
     gradient (autograd maps the gradients of the centred parameters back through the projection) against the fp64 chain
-    on the UNcentred parameters, and against the uncentred fused kernels within the bf16 noise of either."""
+    on the UNcentred parameters, and against the uncentred fused kernels within the bf16 noise of either.
+    The per-feature check of these kernels, on gate-stable rows, is test_occ_mlp_gates_gpu.py."""
     hip = pkg('hipops')
     F = torch.nn.functional
     gen = torch.Generator(device='cpu').manual_seed(21)
@@ -1130,7 +1133,8 @@ def test_occ_mlp_backward_kernels_on_ragged_sizes(n, monkeypatch):
     an odd number of blocks, more blocks than workgroups, more than two rounds): d(x) and every parameter gradient
     against autograd through the fp64 chain, and the two kernels within the same distance of each other (what separates
     any two bf16 evaluations of this chain is a handful of ReLU gates that flip with the rounding of the pre-activations:
-    3-5 % relative L2 at these sizes, for either kernel)."""
+    3-5 % relative L2 at these sizes, for either kernel).
+    The per-feature check of these kernels, on gate-stable rows, is test_occ_mlp_gates_gpu.py."""
     hip = pkg('hipops')
     F = torch.nn.functional
     gen = torch.Generator(device='cpu').manual_seed(100 + n % 97)
