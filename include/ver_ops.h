@@ -384,10 +384,18 @@ int ver_focal_loss_backward_cw(const void* logits, const int64_t* target, const 
  *             mean, rstd f32 [N]
  *   backward: grad_y f32 (+ grad_y_bf16, optional: the gradient that arrived through y_bf16) ->
  *             grad_a (a's dtype), grad_residual f32, grad_gamma / grad_beta f32 [C] (zeroed inside)
+ *   non-finite inputs (tests/test_row_kernels_gpu.py pins this):
+ *     forward : a NaN in residual, or in a KEPT element of a, makes that row's y, y_bf16, mean and rstd NaN and leaves every
+ *             other row bit for bit as it would be without it.  A DROPPED element of a is never multiplied: it contributes
+ *             exactly 0 whatever it holds, a NaN or an infinity included (torch's dropout, mask * a, would propagate it).
  */
 int ver_add_ln_forward(const void* a, int a_dtype, const float* residual, const float* gamma, const float* beta,
                        const int64_t* seed, float p_drop, float eps, float* y, void* y_bf16, float* mean,
                        float* rstd, long N, int C, void* stream);
+/*     backward: the same rows (it reads the forward's NaN mean / rstd) have NaN grad_residual and NaN grad_a in their kept
+ *             elements; grad_a of a dropped element is exactly 0 in every row, those included; grad_gamma is NaN in every
+ *             channel (each sums over that row), grad_beta (a sum of grad_y alone) stays finite; every other row's grad_a
+ *             and grad_residual are bit for bit as without the NaN. */
 int ver_add_ln_backward(const float* grad_y, const void* grad_y_bf16, const void* a, int a_dtype,
                         const float* residual, const float* gamma, const float* mean, const float* rstd,
                         const int64_t* seed, float p_drop, void* grad_a, float* grad_residual, float* grad_gamma,
@@ -395,6 +403,12 @@ int ver_add_ln_backward(const float* grad_y, const void* grad_y_bf16, const void
 /*   y = dropout(relu(x)): the hidden activation of the layer's FFN (mmcv FFN: Linear - ReLU - Dropout - Linear), the
  *   same hash for the keep decision.  backward: grad_x = y > 0 ? grad_y / (1 - p_drop) : 0 (needs y only).
  *   n elements (a multiple of 4), dtype VER_F32 / VER_BF16; y may alias x.
+ *   special values: the gate is the fp32 comparison x > 0, so +-0, negative values and NaN give y = 0; +inf stays +inf, and a
+ *   finite x whose product with 1 / (1 - p_drop) leaves the fp32 range becomes +inf.  Denormals are NOT flushed (the
+ *   library is built with fp32 denormals on): a kept positive denormal x gives the denormal y = x / (1 - p_drop), in fp32
+ *   and in bf16, and the backward, whose only gate is y > 0, passes its gradient -- grad_x != 0 exactly where y != 0.  A
+ *   build that flushes denormals would close the gate for them in both passes alike; callers must not rely on either
+ *   (tests/test_row_kernels_gpu.py asserts the agreement of the two passes, not the fate of a denormal).
  */
 int ver_relu_dropout_forward(const void* x, void* y, const int64_t* seed, float p_drop, long n, int dtype, void* stream);
 int ver_relu_dropout_backward(const void* y, const void* grad_y, void* grad_x, float p_drop, long n, int dtype,
