@@ -87,7 +87,13 @@ int ver_msda_backward(const float* value, const int64_t* shapes_hw, const int64_
  *   VoxelCustomMSDeformableAttention.forward (bevformer/modules/voxel_decoder.py:312-313).
  *   shapes_dhw i64 [levels,3] = (D,H,W); loc f32 [B,Nq,heads,levels,points,3] = (x,y,z) in [0,1];
  *   flat key index = (z*H + y)*W + x; 5-D grid_sample semantics (pixel = loc*size - 0.5, zeros).
- *   Gradient buffers of the backward are caller-allocated and ZERO-INITIALISED.
+ *   Gate: a sample contributes -- to out and to every gradient -- only if -1 < pixel < size on EVERY axis (strict both
+ *   ways; a NaN fails it).  This differs from grid_sample in one point per axis only: at a pixel coordinate of exactly -1
+ *   the corner at 0 has weight 0, so out, grad_value and grad_attn_w are 0 either way, but grid_sample returns a non-zero
+ *   location gradient there and these kernels return 0.  The 2-D op above follows mmcv's rule, which is the same strict gate.
+ *   (tests/test_msda_forms_cpu.py holds both halves: equality with grid_sample elsewhere, its non-zero gradient at -1.)
+ *   Gradient buffers of the backward are caller-allocated and ZERO-INITIALISED: grad_value is accumulated into with
+ *   atomics, grad_loc / grad_attn_w are written for every sample (0 outside the gate).
  */
 int ver_msda3d_forward(const float* value, const int64_t* shapes_dhw, const int64_t* level_start,
                        const float* loc, const float* attn_w, float* out,
