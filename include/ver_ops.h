@@ -375,6 +375,23 @@ int ver_focal_loss_forward_grad_u8_cw(const void* logits, const uint8_t* target,
                                       void* stream);
 int ver_focal_loss_backward_cw(const void* logits, const int64_t* target, const float* class_weight, const float* scale,
                                void* grad, long N, int C, float gamma, float alpha, int dtype, void* stream);
+/*   byte labels for the separate forward and backward passes (additive to ABI 31): ver_focal_loss_forward / _backward and
+ *             their `_cw` twins with target uint8 [N], as ver_focal_loss_forward_grad_u8 takes it -- for a caller whose
+ *             labels are bytes already (the row-order labels ver_occ_targets writes) and who keeps the logits, so that no
+ *             int64 [N] copy of the labels is made in front of the loss.  The same kernels instantiated for the label
+ *             type: the same arithmetic per element, the same partial layout (ver_focal_loss_blocks), the same NaN sum and
+ *             *bad_labels flag for a label outside [0, C] (255, a wrapped -1, among them), hence partials and gradients
+ *             that equal the int64 entries' on the widened labels bit for bit.  Arguments and checks as the int64 entries',
+ *             plus C <= 254 (VER_EINVAL: the classes and the empty label fit a byte; the `_cw` forms' C + 1 <= 256 with
+ *             C % 8 == 0 implies it).  N == 0 as the int64 entries: the `_cw` forms and the backward launch nothing. */
+int ver_focal_loss_forward_u8(const void* logits, const uint8_t* target, float* partial, long N, int C,
+                              float gamma, float alpha, int dtype, int32_t* bad_labels, void* stream);
+int ver_focal_loss_backward_u8(const void* logits, const uint8_t* target, const float* scale, void* grad,
+                               long N, int C, float gamma, float alpha, int dtype, void* stream);
+int ver_focal_loss_forward_u8_cw(const void* logits, const uint8_t* target, const float* class_weight, float* partial,
+                                 long N, int C, float gamma, float alpha, int dtype, int32_t* bad_labels, void* stream);
+int ver_focal_loss_backward_u8_cw(const void* logits, const uint8_t* target, const float* class_weight, const float* scale,
+                                  void* grad, long N, int C, float gamma, float alpha, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * y = LayerNorm(residual + dropout(a)): how both branches of the reference's VoxelFormerLayer end

@@ -216,8 +216,8 @@ __global__ __launch_bounds__(256) void k_focal_fwd(const void* logits, const LT*
     if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-template <bool BF16, bool G2, typename... CW>
-__global__ __launch_bounds__(256) void k_focal_bwd(const void* __restrict__ logits, const int64_t* __restrict__ target,
+template <bool BF16, bool G2, typename LT = int64_t, typename... CW>
+__global__ __launch_bounds__(256) void k_focal_bwd(const void* __restrict__ logits, const LT* __restrict__ target,
                                                    const float* __restrict__ scale, void* __restrict__ grad, long nvec,
                                                    int vec_per_row, float gamma, float alpha, int row_shift,
                                                    CW... class_weight) {
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void k_focal_bwd(const void* __restrict__ logi
     for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += (long)gridDim.x * 256) {
         const long row = row_shift >= 0 ? (v >> row_shift) : v / vec_per_row;
         const int c0 = (int)(v - row * vec_per_row) * 8;
-        const int64_t t64 = target[row];
+        const int64_t t64 = (int64_t)target[row];
         const int tgt = (int)t64;
         float x[8], g[8];
         load_x8<BF16>(logits, v, x);
@@ -373,6 +373,54 @@ extern "C" int ver_focal_loss_backward(const void* logits, const int64_t* target
     return ver_check_launch("ver_focal_loss_backward");
 }
 
+// ---- the separate forward and backward passes on byte labels (C <= 254): further instantiations of the two kernels, for a
+// caller that keeps the logits and holds its labels as bytes (FocalLoss on the row-order labels of ver_occ_targets)
+extern "C" int ver_focal_loss_forward_u8(const void* logits, const uint8_t* target, float* partial, long N, int C,
+                                         float gamma, float alpha, int dtype, int32_t* bad_labels, void* stream) {
+    int rc = check_focal("ver_focal_loss_forward_u8", logits, reinterpret_cast<const int64_t*>(target), N, C, dtype);
+    if (rc) return rc;
+    VER_REQUIRE(C <= 254, VER_EINVAL, "ver_focal_loss_forward_u8: %d classes do not fit byte labels", C);
+    VER_REQUIRE(partial, VER_EINVAL, "ver_focal_loss_forward_u8: null partial-sum buffer");
+    const int blocks = ver_focal_loss_blocks(N, C);
+    const long nvec = N * (long)(C / 8);
+    hipStream_t st = (hipStream_t)stream;
+    const bool g2 = gamma == 2.0f;
+#define VER_FOCAL_FWD8(BF, G2)                                                                                             \
+    hipLaunchKernelGGL((k_focal_fwd<BF, G2, false, uint8_t>), dim3(blocks), dim3(256), 0, st, logits, target, partial, nvec, \
+                       C / 8, gamma, alpha, bad_labels, (void*)nullptr, row_shift_of(C / 8))
+    if (dtype == VER_BF16) {
+        if (g2) VER_FOCAL_FWD8(true, true); else VER_FOCAL_FWD8(true, false);
+    } else {
+        if (g2) VER_FOCAL_FWD8(false, true); else VER_FOCAL_FWD8(false, false);
+    }
+#undef VER_FOCAL_FWD8
+    return ver_check_launch("ver_focal_loss_forward_u8");
+}
+
+extern "C" int ver_focal_loss_backward_u8(const void* logits, const uint8_t* target, const float* scale, void* grad,
+                                          long N, int C, float gamma, float alpha, int dtype, void* stream) {
+    int rc = check_focal("ver_focal_loss_backward_u8", logits, reinterpret_cast<const int64_t*>(target), N, C, dtype);
+    if (rc) return rc;
+    VER_REQUIRE(C <= 254, VER_EINVAL, "ver_focal_loss_backward_u8: %d classes do not fit byte labels", C);
+    if (N == 0) return VER_OK;
+    VER_REQUIRE(scale && grad, VER_EINVAL, "ver_focal_loss_backward_u8: null pointer argument");
+    VER_REQUIRE(((uintptr_t)grad & 15) == 0, VER_EINVAL, "ver_focal_loss_backward_u8: grad must be 16-byte aligned");
+    const int blocks = ver_focal_loss_blocks(N, C);
+    const long nvec = N * (long)(C / 8);
+    hipStream_t st = (hipStream_t)stream;
+    const bool g2 = gamma == 2.0f;
+#define VER_FOCAL_BWD8(BF, G2)                                                                                           \
+    hipLaunchKernelGGL((k_focal_bwd<BF, G2, uint8_t>), dim3(blocks), dim3(256), 0, st, logits, target, scale, grad, nvec, \
+                       C / 8, gamma, alpha, row_shift_of(C / 8))
+    if (dtype == VER_BF16) {
+        if (g2) VER_FOCAL_BWD8(true, true); else VER_FOCAL_BWD8(true, false);
+    } else {
+        if (g2) VER_FOCAL_BWD8(false, true); else VER_FOCAL_BWD8(false, false);
+    }
+#undef VER_FOCAL_BWD8
+    return ver_check_launch("ver_focal_loss_backward_u8");
+}
+
 // ---- class-weighted twins: the same kernels with the table pointer in their trailing pack
 namespace {
 int check_table(const char* who, const float* class_weight, long N, int C) {
@@ -467,9 +515,48 @@ extern "C" int ver_focal_loss_backward_cw(const void* logits, const int64_t* tar
     const long nvec = N * (long)(C / 8);
     hipStream_t st = (hipStream_t)stream;
     const bool g2 = gamma == 2.0f;
-#define VER_K(BF, G2) k_focal_bwd<BF, G2, const float*>
+#define VER_K(BF, G2) k_focal_bwd<BF, G2, int64_t, const float*>
     VER_FOCAL_CW(VER_K, logits, target, scale, grad, nvec, C / 8, gamma, alpha, row_shift_of(C / 8), class_weight);
 #undef VER_K
     return ver_check_launch("ver_focal_loss_backward_cw");
+}
+extern "C" int ver_focal_loss_forward_u8_cw(const void* logits, const uint8_t* target, const float* class_weight, float* partial,
+                                            long N, int C, float gamma, float alpha, int dtype, int32_t* bad_labels, void* stream) {
+    int rc = check_focal("ver_focal_loss_forward_u8_cw", logits, reinterpret_cast<const int64_t*>(target), N, C, dtype);
+    if (rc) return rc;
+    // (C + 1 <= 256 with C % 8 == 0 leaves C <= 248: the labels fit their bytes)
+    rc = check_table("ver_focal_loss_forward_u8_cw", class_weight, N, C);
+    if (rc) return rc;
+    VER_REQUIRE(partial, VER_EINVAL, "ver_focal_loss_forward_u8_cw: null partial-sum buffer");
+    if (N == 0) return VER_OK;
+    const int blocks = ver_focal_loss_blocks(N, C);
+    const long nvec = N * (long)(C / 8);
+    hipStream_t st = (hipStream_t)stream;
+    const bool g2 = gamma == 2.0f;
+#define VER_K(BF, G2) k_focal_fwd<BF, G2, false, uint8_t, const float*>
+    VER_FOCAL_CW(VER_K, logits, target, partial, nvec, C / 8, gamma, alpha, bad_labels, (void*)nullptr, row_shift_of(C / 8),
+                 class_weight);
+#undef VER_K
+    return ver_check_launch("ver_focal_loss_forward_u8_cw");
+}
+
+extern "C" int ver_focal_loss_backward_u8_cw(const void* logits, const uint8_t* target, const float* class_weight,
+                                             const float* scale, void* grad, long N, int C, float gamma, float alpha, int dtype,
+                                             void* stream) {
+    int rc = check_focal("ver_focal_loss_backward_u8_cw", logits, reinterpret_cast<const int64_t*>(target), N, C, dtype);
+    if (rc) return rc;
+    rc = check_table("ver_focal_loss_backward_u8_cw", class_weight, N, C);
+    if (rc) return rc;
+    if (N == 0) return VER_OK;
+    VER_REQUIRE(scale && grad, VER_EINVAL, "ver_focal_loss_backward_u8_cw: null pointer argument");
+    VER_REQUIRE(((uintptr_t)grad & 15) == 0, VER_EINVAL, "ver_focal_loss_backward_u8_cw: grad must be 16-byte aligned");
+    const int blocks = ver_focal_loss_blocks(N, C);
+    const long nvec = N * (long)(C / 8);
+    hipStream_t st = (hipStream_t)stream;
+    const bool g2 = gamma == 2.0f;
+#define VER_K(BF, G2) k_focal_bwd<BF, G2, uint8_t, const float*>
+    VER_FOCAL_CW(VER_K, logits, target, scale, grad, nvec, C / 8, gamma, alpha, row_shift_of(C / 8), class_weight);
+#undef VER_K
+    return ver_check_launch("ver_focal_loss_backward_u8_cw");
 }
 #undef VER_FOCAL_CW

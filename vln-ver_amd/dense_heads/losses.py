@@ -60,8 +60,14 @@ class FocalLoss(nn.Module):
     def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, class_weight=None):
         """``class_weight`` (extension of mmdet's signature): fp32 [C + 1], one factor per label value in [0, C]; row n is
         multiplied by class_weight[target[n]] -- the reference's ``weight=weights[gt_occupancy]`` (head:1417-1425) without
-        the [N] tensor.  ``avg_factor`` is the caller's and stays unweighted."""
+        the [N] tensor.  ``avg_factor`` is the caller's and stays unweighted.  ``target`` may be uint8 on the GPU (C <= 254):
+        the fused path reads the bytes as they are (``ver_focal_loss_*_u8``), the same loss and gradient bit for bit as on
+        the widened labels."""
         reduction = reduction_override if reduction_override else self.reduction
+        if target.dtype == torch.uint8 and not (pred.is_cuda and target.is_cuda):
+            # byte labels are the form the HIP kernels read (ver_focal_loss_*_u8; an ``OccupancyTargets``' labels): no CPU form
+            raise RuntimeError('FocalLoss: uint8 targets must be a GPU tensor next to GPU logits: byte labels only exist for '
+                               'the HIP kernels (widen them with .long() for the torch formulas)')
         if (pred.is_cuda and weight is None and reduction == 'mean' and avg_factor is not None
                 and pred.dim() == 2 and pred.size(1) % 8 == 0 and pred.size(0) >= 4096
                 and pred.dtype in (torch.float32, torch.bfloat16)):
@@ -76,6 +82,8 @@ class FocalLoss(nn.Module):
             from ..hipops import sigmoid_focal_loss_sum
             return self.loss_weight * (sigmoid_focal_loss_sum(pred, target, self.gamma, self.alpha, class_weight)
                                        / avg_factor)
+        if target.dtype == torch.uint8:                       # (a call the kernels are not built for: the torch formulas index)
+            target = target.long()
         if class_weight is not None:
             # the lookup uses a clamped index: a label outside [0, C] raises in F.one_hot below, as without weights, and
             # never becomes an out-of-bounds index

@@ -83,9 +83,10 @@ def count_occupied(occupied, by_words=True):
 def loss_labels(labels, classes, plan=None, bs=None, zdim=1, as_bytes=False):
     """``(gt, avg)`` of the occupancy loss: one label per logit row, flat, and the number of occupied voxels.  ``labels``: a
     dense tensor in the reference's voxel order or an ``OccupancyTargets``; ``plan``: the logits are in that plan's row order
-    (``bs`` samples of ``zdim`` layers), None: in the voxel order.  ``as_bytes``: for the fused MLP + focal-loss Function,
-    whose kernel reads byte labels as they are (ver_focal_loss_forward_grad_u8); otherwise for the registered loss, which
-    takes int64 targets (``ver_focal_loss_forward``, ``F.one_hot``) -- the bytes of an ``OccupancyTargets`` are widened."""
+    (``bs`` samples of ``zdim`` layers), None: in the voxel order.  ``as_bytes``: for a consumer whose kernels read byte
+    labels as they are -- the fused MLP + focal-loss Function (ver_focal_loss_forward_grad_u8), and ``FocalLoss`` on the GPU
+    for the labels of an ``OccupancyTargets`` (ver_focal_loss_forward_u8 / _backward_u8); otherwise for the torch formulas
+    of the registered loss (``F.one_hot``), which index with int64 -- the bytes of an ``OccupancyTargets`` are widened."""
     if isinstance(labels, OccupancyTargets):
         # byte labels in either order and the occupied count: nothing to clamp, narrow or reduce
         gt = labels.ordered('rows' if plan is not None else 'voxels', plan)

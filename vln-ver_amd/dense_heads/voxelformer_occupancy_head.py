@@ -650,14 +650,15 @@ class VoxelFormerOccupancyHead(BaseModule):
         times the factor of its label, as ``loss_only_occupancy`` does with ``occ_weights`` (head:1417-1425); the
         normaliser stays the unweighted count.
         An ``OccupancyTargets`` brings its labels in the order of the logits and ``count[-1]`` as the normaliser: no
-        compare, no reduction over the labels."""
+        compare, no reduction over the labels -- and on the GPU no widening: ``FocalLoss`` reads the bytes."""
         plan = bs = None
         if isinstance(occupancy_preds, tuple):                         # (logits in GEMM row order, plan, bs)
             occupancy_preds, plan, bs = occupancy_preds               # [bs*X*Y, Z, classes], group-major rows
         preds = occupancy_preds.reshape(-1, self.occupancy_classes)
         if not (preds.is_cuda and preds.dtype == torch.bfloat16):     # the fused loss reads bf16 as is
             preds = preds.float()
-        gt, avg = loss_labels(gt_occupancy, self.occupancy_classes, plan, bs, self.occ_zdim)
+        gt, avg = loss_labels(gt_occupancy, self.occupancy_classes, plan, bs, self.occ_zdim,
+                              as_bytes=isinstance(gt_occupancy, OccupancyTargets) and preds.is_cuda)
         gt, avg = gt.to(preds.device), avg.to(preds.device)
         table = self.class_weight_table(class_weights, preds.device)
         if table is None:

@@ -1,5 +1,5 @@
-"""hipGraph replay of the head (``GraphedHead``) and of the whole lifting step (``GraphedLiftStep``) for small, launch-bound
-batches.
+"""hipGraph replay of the head (``GraphedHead``), of the whole lifting step (``GraphedLiftStep``) and of the whole multi-task
+training step with fresh ground truth per replay (``GraphedTrainStep``) for small, launch-bound batches.
 
 At the reference's own batch point (vocc.py: ``samples_per_gpu=1``) the full multi-task step is bound by the HOST: ~1 500
 module calls forward and as many autograd nodes backward, 13-16 ms + 23-28 ms of Python / dispatcher time around ~20 ms of
@@ -184,3 +184,228 @@ class GraphedLiftStep:
                     'first GPU call of the process (memset nodes are not ordered against the kernels behind them otherwise); '
                     'importing vln-ver_amd sets it, but only takes effect if HIP was not initialised earlier.')
         return self.loss
+
+
+class MultiTaskStep(torch.nn.Module):
+    """The full multi-task training step's forward, from tensors of fixed shapes to the loss dict, through the head's public
+    API alone: ``head(..., occupancy_rows=True)``, ``head.occupancy_targets_device`` on the packed sparse pairs
+    (``ver_occ_targets``: byte labels in the GEMMs' row order) and ``head.loss`` with a ``PaddedGts`` -- with
+    ``train_cfg.assigner.solver = 'fused'`` nothing in it touches the host after its first call, so ``GraphedTrainStep`` can
+    capture it; called eagerly it is that step's twin.  ``autocast_dtype``: torch.bfloat16 as ``bench.py`` trains, None =
+    fp32.  ``targets`` holds the ``OccupancyTargets`` of the last call (its ``bad`` counters: ``GraphedTrainStep.flags``)."""
+
+    def __init__(self, head, autocast_dtype=torch.bfloat16):
+        super().__init__()
+        self.head, self.autocast_dtype = head, autocast_dtype
+        self.targets = None
+
+    def forward(self, feats, world2pixel, origin, gts, occ):
+        """feats [Ncam, B, Nk, C], world2pixel [B, Ncam, 4, 4], origin [B, 3]; gts: ``PaddedGts`` (``head.pad_gts``); occ:
+        ``hipops.PackedOccGts`` on the GPU -- pairs at or past ``occ.offsets[B]`` belong to no sample."""
+        head = self.head
+        with torch.autocast('cuda', dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None,
+                            cache_enabled=False):
+            outs = head(feats, None, world2pixel=world2pixel, origin=origin, occupancy_rows=True)
+        outs = {k: (v.float() if torch.is_tensor(v) and k != 'occupancy_preds' else v) for k, v in outs.items()}
+        self.targets = head.occupancy_targets_device(occ, device=feats.device)
+        return head.loss(gts, None, self.targets, outs)
+
+
+def check_step_inputs(who, captured, offered):
+    """The host-side size checks of ``GraphedTrainStep``, on host data alone: ``captured`` and ``offered`` are sequences of
+    ``(name, shape, dtype, ragged)`` of the static buffers and of a call's tensors.  ``ragged`` names the axis along which
+    a call may bring LESS than the buffer holds (boxes per sample, pairs) and the limit's name; every other axis, and the
+    dtype, must be what was captured.  Raises ``ValueError``."""
+    for (name, shape, dtype, ragged), (_, got, got_dtype, _) in zip(captured, offered):
+        shape, got = tuple(shape), tuple(got)
+        if ragged is not None and len(got) == len(shape) and got[ragged[0]] > shape[ragged[0]]:
+            raise ValueError('%s: %s holds %d %s, the %s captured is %d' % (who, name, got[ragged[0]], ragged[1], ragged[2],
+                                                                            shape[ragged[0]]))
+        same = len(got) == len(shape) and all(a == b or (ragged is not None and i == ragged[0]) for i, (a, b) in enumerate(zip(got, shape)))
+        if not same or got_dtype != dtype:
+            raise ValueError('%s: %s is %s %s, captured with %s %s' % (who, name, got, got_dtype, shape, dtype))
+
+
+class GraphedTrainStep:
+    """One training step of the WHOLE head -- encoder, detection decoder, cls / reg branches, coarse-to-fine occupancy,
+    occupancy targets from the sparse pairs, the set loss of every decoder layer, the occupancy focal loss, backward, gradient
+    clipping + AdamW -- for one fixed batch shape and one rank, captured as a SINGLE hipGraph and replayed with fresh ground
+    truth: nothing between the inputs and the updated parameters runs on the host (``GraphedHead`` replays two graphs around
+    a host-side Hungarian solve, eager loss terms and an eager optimizer).  Same kernels, same arithmetic as the eager step.
+
+    ``model``: a ``MultiTaskStep`` (or a module with its signature and a ``head``); its head must use
+    ``train_cfg.assigner.solver = 'fused'`` -- costs, ``ver_lsa_solve``, normalisers and the set loss on the device -- and be
+    the default multi-task head (no ``add_layout``, ``only_occ``, ``only_det``, ``getbev``); ``optimizer``: an
+    ``optim.ClipAdamW`` over the trainable parameters.  The sample inputs fix every shape:
+
+    * ``feats [Ncam, B, Nk, C]``, ``world2pixel [B, Ncam, 4, 4]``, ``origin [B, 3]``;
+    * ``gts``: a ``PaddedGts`` as ``head.pad_gts(..., capacity=)`` makes it; its width is the box ``capacity`` of every later
+      call, which may bring a narrower one (copied into the leading columns; the counts bound what is read);
+    * ``occ``: a ``hipops.PackedOccGts`` on the GPU without invalid voxels; ``pair_capacity`` (default: its pair count) is the
+      most pairs a later call may bring.  ``ver_occ_targets`` runs inside the graph over the whole pair buffer with the
+      offsets delimiting the live pairs: every sample visits ``[offsets[b], offsets[b + 1])`` and nothing else, so the
+      stale pairs past ``offsets[B]`` of a longer earlier step are applied to no sample.
+
+    Construction follows ``GraphedLiftStep``: ``warmup`` REAL eager steps on a side stream (they train the model; the
+    first-call host checks -- label range, ``OccupancyTargets.check``, the assignment flag -- the library handles and the row
+    plan happen there and never under capture), the live-loss check, ``optimizer.prepare_capture()``, one capture on one
+    stream.  Everything said there about eager steps of the same optimizer between replays and about replaced optimizer
+    buffers holds here.
+
+    ``losses = step(feats, w2p, origin, gts, occ)`` copies the inputs into the static buffers (unless they ARE those buffers:
+    ``step.inputs``, ``step.gts``, ``step.occ``) and returns the loss dict: STATIC tensors, overwritten by the next call
+    (``float()`` or clone what has to survive it); ``step.total`` is their sum, ``step.grad_norm`` the clip norm.  Refusals are
+    decided from sizes the host knows, never from a device read; what only the device knows -- an assignment problem, a pair
+    with a class or voxel out of range, a label outside [0, C] -- is not read in the call: ``flags()`` reads it on demand."""
+
+    def __init__(self, model, optimizer, feats, world2pixel, origin, gts, occ, pair_capacity=None, warmup=3,
+                 check_live_losses=True):
+        from .dense_heads.voxelformer_occupancy_head import PaddedGts
+        from .hipops import PackedOccGts
+        who = 'GraphedTrainStep'
+        if isinstance(model, torch.nn.parallel.DistributedDataParallel) or \
+                isinstance(getattr(model, 'head', None), torch.nn.parallel.DistributedDataParallel):
+            raise RuntimeError('%s: a DistributedDataParallel model: the gradient all-reduce is not part of the graph (one '
+                               'rank only)' % who)
+        if not hasattr(optimizer, 'prepare_capture'):
+            raise TypeError('%s needs an optimizer whose step() can be captured (optim.ClipAdamW)' % who)
+        head = model.head
+        self._check_head(head)
+        if not isinstance(gts, PaddedGts) or not isinstance(occ, PackedOccGts):
+            raise TypeError('%s: gts is a PaddedGts (head.pad_gts), occ a hipops.PackedOccGts' % who)
+        if occ.has_invalid:
+            raise ValueError('%s: a PackedOccGts with invalid voxels (evaluation labels) is not a training target' % who)
+        bs = feats.shape[1]
+        pair_capacity = occ.n_total if pair_capacity is None else int(pair_capacity)
+        if occ.n_total > pair_capacity:
+            raise ValueError('%s: occ holds %d pairs, the pair capacity is %d' % (who, occ.n_total, pair_capacity))
+        if occ.bs != bs or gts.boxes.shape[0] != bs:
+            raise ValueError('%s: %d samples of features, %d of boxes, %d of pairs' % (who, bs, gts.boxes.shape[0], occ.bs))
+        self._need_gpu(feats, world2pixel, origin, gts, occ)
+        self.model, self.optimizer = model, optimizer
+        self.capacity, self.pair_capacity = int(gts.boxes.shape[1]), pair_capacity
+        self.inputs = tuple(t.detach().clone() for t in (feats, world2pixel, origin))
+        self.gts = PaddedGts(*(t.detach().clone() for t in gts))
+        # the layout of a PackedOccGts at the pair capacity; pairs past the live ones start out as (0, 0) and belong to no sample
+        buffer = torch.zeros(2 * (bs + 1) + 2 * pair_capacity, dtype=torch.int32, device=feats.device)
+        self.occ = PackedOccGts(buffer, bs, pair_capacity, 0, False)
+        self._load_gts(gts, occ)
+        self.training = model.training
+        static = self.inputs + (self.gts, self.occ)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            norm = None
+            for _ in range(max(1, warmup)):                 # (at least one: the optimizer state must exist before the capture)
+                optimizer.zero_grad(set_to_none=True)
+                total = sum(model(*static).values())
+                total.backward()
+                norm = optimizer.step()
+            self._clean_warmup = norm is not None and bool(torch.isfinite(norm))
+            self._unchecked = 3
+            total = None
+            optimizer.zero_grad(set_to_none=True)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        if check_live_losses:
+            gc.collect()
+            n = len(_live_losses())
+            if n:
+                raise RuntimeError('%s: %d scalar tensor(s) with an autograd graph are still alive (losses of earlier eager '
+                                   'steps?); drop them before building the graph (see GraphedHead)' % (who, n))
+        optimizer.prepare_capture()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            losses = model(*static)
+            total = sum(losses.values())
+            total.backward()
+            self.grad_norm = optimizer.step()
+            self.losses = {k: v.detach() for k, v in losses.items()}
+            self.total = total.detach()
+        self._targets = model.targets                      # the capture's OccupancyTargets: static tensors the replays rewrite
+        losses = total = None
+
+    @staticmethod
+    def _check_head(head):
+        who = 'GraphedTrainStep'
+        solver = getattr(getattr(head, 'assigner', None), 'solver', 'host')
+        if solver != 'fused':
+            raise ValueError("%s: train_cfg.assigner.solver is %r; the captured step needs 'fused' (costs, assignment and set "
+                             'loss on the device, nothing solved on the host)' % (who, solver))
+        if head.add_layout:
+            raise NotImplementedError('%s: add_layout=True: the room-layout terms are not part of the captured step' % who)
+        if head.only_occ or head.only_det:
+            raise NotImplementedError('%s covers the default multi-task branch of the head (only_occ / only_det are set)' % who)
+        if getattr(head, 'getbev', None) is not None:
+            raise NotImplementedError('%s: a head built with getbev=<store> writes volumes to the host inside forward (device '
+                                      '-> host copies and file I/O), which cannot be captured' % who)
+
+    @staticmethod
+    def _need_gpu(feats, world2pixel, origin, gts, occ):
+        named = (('feats', feats), ('world2pixel', world2pixel), ('origin', origin), ('gts.boxes', gts.boxes),
+                 ('gts.labels', gts.labels), ('gts.counts', gts.counts), ('occ.buffer', occ.buffer))
+        cpu = [k for k, t in named if not t.is_cuda]
+        if cpu:
+            raise RuntimeError('GraphedTrainStep needs GPU tensors (HIP graphs); on the CPU: %s' % ', '.join(cpu))
+
+    @staticmethod
+    def _signature(feats, world2pixel, origin, gts, n_pairs, n_offsets):
+        boxes = ('boxes per sample', 'box capacity')
+        return (('feats', feats.shape, feats.dtype, None), ('world2pixel', world2pixel.shape, world2pixel.dtype, None),
+                ('origin', origin.shape, origin.dtype, None), ('gts.boxes', gts.boxes.shape, gts.boxes.dtype, (1,) + boxes),
+                ('gts.labels', gts.labels.shape, gts.labels.dtype, (1,) + boxes),
+                ('gts.counts', gts.counts.shape, gts.counts.dtype, None),
+                ('occ.pairs', (n_pairs, 2), torch.int32, (0, 'pairs', 'pair capacity')),
+                ('occ.offsets', (n_offsets,), torch.int32, None))
+
+    def _load_gts(self, gts, occ):
+        """Ground truth of a call into the static buffers: the leading columns of the box tables, the counts, the live pairs
+        and their offsets (what lies behind them is never read: the counts and the offsets bound every kernel's loops)."""
+        if gts is not self.gts:
+            n = gts.boxes.shape[1]
+            self.gts.boxes[:, :n].copy_(gts.boxes, non_blocking=True)
+            self.gts.labels[:, :n].copy_(gts.labels, non_blocking=True)
+            self.gts.counts.copy_(gts.counts, non_blocking=True)
+        if occ is not self.occ:
+            self.occ.offsets.copy_(occ.offsets, non_blocking=True)
+            self.occ.pairs[:occ.n_total].copy_(occ.pairs, non_blocking=True)
+
+    def __call__(self, feats, world2pixel, origin, gts, occ):
+        who = 'GraphedTrainStep'
+        if self.model.training != self.training:
+            raise RuntimeError('%s: model.training differs from capture time; build a new one for the new mode' % who)
+        if not isinstance(gts, type(self.gts)) or not isinstance(occ, type(self.occ)):
+            raise TypeError('%s: gts is a PaddedGts (head.pad_gts), occ a hipops.PackedOccGts' % who)
+        self._need_gpu(feats, world2pixel, origin, gts, occ)
+        if occ is not self.occ and occ.has_invalid:
+            raise ValueError('%s: a PackedOccGts with invalid voxels (evaluation labels) is not a training target' % who)
+        check_step_inputs(who, self._signature(*self.inputs, self.gts, self.pair_capacity, self.occ.bs + 1),
+                          self._signature(feats, world2pixel, origin, gts, occ.n_total, occ.bs + 1))
+        for dst, src in zip(self.inputs, (feats, world2pixel, origin)):
+            if src is not dst:
+                dst.copy_(src, non_blocking=True)
+        self._load_gts(gts, occ)
+        self.optimizer.refresh()
+        self.graph.replay()
+        self.optimizer.replayed()
+        if self._unchecked:
+            # as GraphedLiftStep: the first replays are checked (one synchronisation each) for the runtime's memset-node problem
+            self._unchecked -= 1
+            if not bool(torch.isfinite(self.grad_norm)) and self._clean_warmup:
+                raise RuntimeError(
+                    '%s: the gradient norm of a replayed step is not finite although the eager warm-up steps were clean.  On '
+                    'ROCm 7.2 hipGraph replay needs DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 in the environment BEFORE the first GPU '
+                    'call of the process (memset nodes are not ordered against the kernels behind them otherwise); importing '
+                    'vln-ver_amd sets it, but only takes effect if HIP was not initialised earlier.' % who)
+        return self.losses
+
+    def flags(self):
+        """What the replayed steps could only report on the device, read now (ONE synchronisation): ``assignment`` -- the
+        sticky ``AssignmentFlag`` (a cost matrix ``lsa_solve`` could not assign); ``label_range`` -- the sticky
+        ``LabelRangeFlag`` (a label outside [0, C] reached the focal loss); ``rejected_pairs`` / ``lost_listings`` -- ``bad``
+        of the LAST step's occupancy targets (pairs with a voxel or class out of range; listings of a voxel that lost to a
+        larger class).  All zero for clean steps; nothing is raised or reset here."""
+        from .hipops import AssignmentFlag, LabelRangeFlag
+        dev = self.total.device
+        values = torch.cat([AssignmentFlag.of(dev).dev, LabelRangeFlag.of(dev).dev, self._targets.bad]).tolist()
+        return dict(zip(('assignment', 'label_range', 'rejected_pairs', 'lost_listings'), values))

@@ -833,7 +833,9 @@ class SigmoidFocalLossSumFunction(Function):
     """sum over all elements of mmdet's sigmoid focal loss (ver_focal_loss_forward / _backward):
     logits fp32|bf16 [N, C] with C % 8 == 0, target int64 [N] in [0, C]; returns an fp32 scalar.
     ``class_weight`` (fp32 [C + 1] or None): row n is multiplied by class_weight[target[n]] (the ``_cw`` entries); no
-    gradient flows to it."""
+    gradient flows to it.  uint8 targets (C <= 254; the labels of an ``OccupancyTargets``) are read as they are by the
+    ``_u8`` entries -- the same partials and gradients, bit for bit, without an int64 [N] copy; every other integer dtype
+    is widened to int64."""
 
     @staticmethod
     def forward(ctx, logits, target, gamma, alpha, class_weight=None):
@@ -841,22 +843,29 @@ class SigmoidFocalLossSumFunction(Function):
         if logits.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError('logits must be fp32 or bf16')
         logits = logits.contiguous()
-        target = _gpu(target, 'target').to(torch.int64).contiguous()
+        target = _gpu(target, 'target')
+        if target.dtype != torch.uint8:
+            target = target.to(torch.int64).contiguous()
         n, c = logits.shape
         if target.shape != (n,):
             raise ValueError('target must be [N]')
+        u8 = '_u8' if target.dtype == torch.uint8 else ''
+        if u8 and c > 254:
+            raise ValueError('uint8 targets hold at most 254 classes and the empty label, got %d classes' % c)
         dt = 1 if logits.dtype == torch.bfloat16 else 0
         blocks = lib().ver_focal_loss_blocks(n, c)
         partial = torch.zeros(blocks, dtype=torch.float32, device=logits.device)
         flag = LabelRangeFlag.of(logits.device)
         flag.poll()                                          # a bad label of an EARLIER call is reported here
         if class_weight is None:
-            _launch('ver_focal_loss_forward', lambda: lib().ver_focal_loss_forward(
+            entry = getattr(lib(), 'ver_focal_loss_forward' + u8)
+            _launch('ver_focal_loss_forward' + u8, lambda: entry(
                 _p(logits), _p(target), _p(partial), n, c, gamma, alpha, dt, _p(flag.dev), _stream()))
             ctx.save_for_backward(logits, target)
         else:
             table = _class_weight_table(class_weight, c, logits.device)
-            _launch('ver_focal_loss_forward_cw', lambda: lib().ver_focal_loss_forward_cw(
+            entry = getattr(lib(), 'ver_focal_loss_forward%s_cw' % u8)
+            _launch('ver_focal_loss_forward%s_cw' % u8, lambda: entry(
                 _p(logits), _p(target), _p(table), _p(partial), n, c, gamma, alpha, dt, _p(flag.dev), _stream()))
             ctx.save_for_backward(logits, target, table)
         flag.mirror(c)
@@ -871,12 +880,15 @@ class SigmoidFocalLossSumFunction(Function):
         n, c = logits.shape
         scale = _gpu(grad_out, 'grad_out').float().reshape(1).contiguous()
         grad = torch.empty_like(logits)
+        u8 = '_u8' if target.dtype == torch.uint8 else ''
         if len(ctx.saved_tensors) == 2:
-            _launch('ver_focal_loss_backward', lambda: lib().ver_focal_loss_backward(
+            entry = getattr(lib(), 'ver_focal_loss_backward' + u8)
+            _launch('ver_focal_loss_backward' + u8, lambda: entry(
                 _p(logits), _p(target), _p(scale), _p(grad), n, c, gamma, alpha, dt, _stream()))
         else:
             table = ctx.saved_tensors[2]
-            _launch('ver_focal_loss_backward_cw', lambda: lib().ver_focal_loss_backward_cw(
+            entry = getattr(lib(), 'ver_focal_loss_backward%s_cw' % u8)
+            _launch('ver_focal_loss_backward%s_cw' % u8, lambda: entry(
                 _p(logits), _p(target), _p(table), _p(scale), _p(grad), n, c, gamma, alpha, dt, _stream()))
         return grad, None, None, None, None
 
