@@ -689,6 +689,37 @@ int ver_clip_adamw_step_tensors(void* const* table, const long* sizes, const int
                                 const float* hyper, int* steps, int n_tensors, int n_chunks, int chunk_elems, float* partial,
                                 float* norm_out, float max_norm, void* stream);
 
+/* Gradient exchange through ONE flat buffer (added under ABI 31; data-parallel training without DistributedDataParallel's
+ * bucket hooks, so that the step can live in captured hipGraphs: graph A ends in ver_grad_pack, one eager all-reduce of
+ * `flat` follows, graph B is ver_clip_adamw_step_flat -- vln-ver_amd/ddp.py GradExchange).
+ *   offsets      device long [n_tensors]: first element of tensor t inside `flat`; every offset a multiple of 8 elements,
+ *                tensors in order and not overlapping (running sum of the sizes, each rounded up to 8)
+ *   flat         device buffer, 16-byte aligned, f32 | bf16 (flat_dtype = VER_F32 | VER_BF16)
+ *   sizes, chunk_tensor, chunk_index, n_tensors, n_chunks, chunk_elems: the chunk tables of ver_clip_adamw_step above
+ *
+ * ver_grad_pack: flat[offsets[t] + i] = g_t[i] * scale for every tensor, one launch.
+ *   table        device array of n_tensors pointers: the f32 gradients, each at least 4-byte aligned (16-byte aligned ones
+ *                move 16 bytes per lane and store, any other -- a view into a bucket -- goes element by element)
+ *   scale        1 / world size for a mean of the ranks' gradients; the product is formed in fp32
+ *   VER_F32: the product is stored as computed.  VER_BF16: it is rounded ONCE, to nearest-even; a NaN is stored as the
+ *   quiet NaN 0x7fc0, +-inf stay +-inf, a finite product past the largest bf16 becomes +-inf (round-to-nearest).
+ *   The elements of `flat` between the tensors (the padding up to the next multiple of 8) are never written. */
+int ver_grad_pack(const void* const* table, const long* sizes, const long* offsets, const int* chunk_tensor,
+                  const int* chunk_index, int n_tensors, int n_chunks, int chunk_elems, float scale, void* flat,
+                  int flat_dtype, void* stream);
+
+/* ver_clip_adamw_step_flat: ver_clip_adamw_step_tensors with the gradient of tensor t read from flat + offsets[t] in
+ * flat_dtype (bf16 widened to fp32 on load) instead of through the table.
+ *   table        keeps its [4][n_tensors] layout (parameters | gradients | exp_avg | exp_avg_sq); the gradient row is NOT read
+ * Every result -- parameters, both moments, `steps`, norm_out -- is bit for bit what ver_clip_adamw_step_tensors gives on
+ * 16-byte-aligned f32 gradient tensors holding the same values: both are one kernel body over two gradient loaders, so the
+ * order of the sum of squares (lane i of 256 takes elements 4(i + 256k) .. +3, the tail element by element, the block sum,
+ * the in-order sum of the partials in every workgroup) is the same. */
+int ver_clip_adamw_step_flat(void* const* table, const long* sizes, const long* offsets, const int* chunk_tensor,
+                             const int* chunk_index, const float* hyper, int* steps, const void* flat, int flat_dtype,
+                             int n_tensors, int n_chunks, int chunk_elems, float* partial, float* norm_out, float max_norm,
+                             void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Hungarian target assignment (ABI 31): a batch of rectangular linear sum assignment problems, with the semantics of
  * `scipy.optimize.linear_sum_assignment(cost[p, :, :ncols[p]])` as the reference calls it per (decoder layer, sample) at

@@ -25,38 +25,101 @@ __device__ __forceinline__ float block_sum(float v) {
     __syncthreads();
     return red[0] + red[1] + red[2] + red[3];
 }
+
+__device__ __forceinline__ float bf16_widen(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
+
+// fp32 -> bf16, one rounding to nearest-even; NaN -> the quiet NaN 0x7fc0, +-inf stay (c10::BFloat16's rule: pack_host in
+// hipops.py is the host model)
+__device__ __forceinline__ unsigned short bf16_round(float f) {
+    const unsigned u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
+    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+// Where k_sqnorm / k_clip_adamw read the gradient of tensor t from: `at(t, start)` -> a cursor with `wide()` (16-byte loads
+// of four elements are legal), `v4(i)` (elements 4i .. 4i+3) and `el(i)`, all as fp32.  One kernel body per loader, so the
+// order of every sum and the compiler's contractions are those of the fp32 pointer-table form.
+struct TableGrads {              // row 1 of the [4][n] pointer table: fp32 tensors of any 4-byte alignment
+    const float* const* table;
+    int n;
+    struct Cursor {
+        const float* g;
+        __device__ bool wide() const { return (reinterpret_cast<uintptr_t>(g) & 15) == 0; }
+        __device__ float4 v4(long i) const { return reinterpret_cast<const float4*>(g)[i]; }
+        __device__ float el(long i) const { return g[i]; }
+    };
+    __device__ Cursor at(int t, long start) const { return {table[n + t] + start}; }
+};
+
+// flat + offsets[t]: offsets are multiples of 8 elements, chunk starts multiples of 4, flat itself 16-byte aligned -- four
+// elements are always one aligned load (16 bytes of fp32, 8 of bf16)
+struct FlatGradsF32 {
+    const float* flat;
+    const long* offsets;
+    struct Cursor {
+        const float* g;
+        __device__ bool wide() const { return true; }
+        __device__ float4 v4(long i) const { return reinterpret_cast<const float4*>(g)[i]; }
+        __device__ float el(long i) const { return g[i]; }
+    };
+    __device__ Cursor at(int t, long start) const { return {flat + offsets[t] + start}; }
+};
+
+struct FlatGradsBF16 {
+    const unsigned short* flat;
+    const long* offsets;
+    struct Cursor {
+        const unsigned short* g;
+        __device__ bool wide() const { return true; }
+        __device__ float4 v4(long i) const {
+            const ushort4 q = reinterpret_cast<const ushort4*>(g)[i];
+            return make_float4(bf16_widen(q.x), bf16_widen(q.y), bf16_widen(q.z), bf16_widen(q.w));
+        }
+        __device__ float el(long i) const { return bf16_widen(g[i]); }
+    };
+    __device__ Cursor at(int t, long start) const { return {flat + offsets[t] + start}; }
+};
 }  // namespace
 
-// table: [4][n] device pointers (p | g | m | v), sizes [n], chunk_tensor [n_chunks], chunk_index [n_chunks] (index of the
-// chunk inside its tensor)
-__global__ __launch_bounds__(256) void k_sqnorm(const float* const* __restrict__ table, const long* __restrict__ sizes,
+// grads: one of the loaders above; sizes [n], chunk_tensor [n_chunks], chunk_index [n_chunks] (index of the chunk inside its
+// tensor)
+template <class Grads>
+__global__ __launch_bounds__(256) void k_sqnorm(const Grads grads, const long* __restrict__ sizes,
                                                 const int* __restrict__ chunk_tensor, const int* __restrict__ chunk_index,
-                                                int n, int chunk, float* __restrict__ partial, int* __restrict__ steps) {
+                                                int chunk, float* __restrict__ partial, int* __restrict__ steps) {
     const int t = chunk_tensor[blockIdx.x];
     // per-tensor update counters kept on the device (ver_clip_adamw_step_tensors): the first chunk of a tensor counts this
     // update; k_clip_adamw, next on the stream, reads the new count for its bias corrections
     if (steps && chunk_index[blockIdx.x] == 0 && threadIdx.x == 0) steps[t] += 1;
     const long start = (long)chunk_index[blockIdx.x] * chunk;
     const long len = min((long)chunk, sizes[t] - start);
-    const float* g = table[n + t] + start;
+    const typename Grads::Cursor g = grads.at(t, start);
     float s = 0.f;
-    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+    if (g.wide()) {
         const long nv = len >> 2;
         for (long i = threadIdx.x; i < nv; i += 256) {
-            const float4 q = reinterpret_cast<const float4*>(g)[i];
+            const float4 q = g.v4(i);
             s += q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
         }
-        for (long i = (nv << 2) + threadIdx.x; i < len; i += 256) s += g[i] * g[i];
+        for (long i = (nv << 2) + threadIdx.x; i < len; i += 256) {
+            const float e = g.el(i);
+            s += e * e;
+        }
     } else {
-        for (long i = threadIdx.x; i < len; i += 256) s += g[i] * g[i];
+        for (long i = threadIdx.x; i < len; i += 256) {
+            const float e = g.el(i);
+            s += e * e;
+        }
     }
     s = block_sum(s);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // hyper (or NULL: the scalar arguments hold for every tensor): [n][6] floats per tensor = lr, beta1, beta2, eps, weight decay,
-// (unused); steps (with hyper): the number of updates of tensor t INCLUDING this one (k_sqnorm has counted it)
-__global__ __launch_bounds__(256) void k_clip_adamw(float* const* __restrict__ table, const long* __restrict__ sizes,
+// (unused); steps (with hyper): the number of updates of tensor t INCLUDING this one (k_sqnorm has counted it).  table: [4][n]
+// device pointers (p | g | m | v); the gradient comes through `grads`, which may or may not read row 1
+template <class Grads>
+__global__ __launch_bounds__(256) void k_clip_adamw(const Grads grads, float* const* __restrict__ table, const long* __restrict__ sizes,
                                                     const int* __restrict__ chunk_tensor, const int* __restrict__ chunk_index,
                                                     int n, int chunk, const float* __restrict__ partial, int n_chunks,
                                                     float max_norm, float lr, float beta1, float beta2, float eps, float decay,
@@ -79,7 +142,7 @@ __global__ __launch_bounds__(256) void k_clip_adamw(float* const* __restrict__ t
     const long start = (long)chunk_index[blockIdx.x] * chunk;
     const long len = min((long)chunk, sizes[t] - start);
     float* p = table[t] + start;
-    const float* g = table[n + t] + start;
+    const typename Grads::Cursor g = grads.at(t, start);
     float* m = table[2 * n + t] + start;
     float* v = table[3 * n + t] + start;
     if (hyper) {
@@ -97,14 +160,14 @@ __global__ __launch_bounds__(256) void k_clip_adamw(float* const* __restrict__ t
         vv = beta2 * vv + (1.f - beta2) * gg * gg;
         pp -= step_size * mm / (sqrtf(vv) * inv_sqrt_bc2 + eps);
     };
-    const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                       reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+    const bool vec = g.wide() && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) |
+                                   reinterpret_cast<uintptr_t>(v)) & 15) == 0;
     long done = 0;
     if (vec) {
         const long nv = len >> 2;
         for (long i = threadIdx.x; i < nv; i += 256) {
             float4 pp = reinterpret_cast<float4*>(p)[i], mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
-            const float4 gg = reinterpret_cast<const float4*>(g)[i];
+            const float4 gg = g.v4(i);
             upd(pp.x, gg.x, mm.x, vv.x), upd(pp.y, gg.y, mm.y, vv.y), upd(pp.z, gg.z, mm.z, vv.z), upd(pp.w, gg.w, mm.w, vv.w);
             reinterpret_cast<float4*>(p)[i] = pp, reinterpret_cast<float4*>(m)[i] = mm, reinterpret_cast<float4*>(v)[i] = vv;
         }
@@ -112,7 +175,7 @@ __global__ __launch_bounds__(256) void k_clip_adamw(float* const* __restrict__ t
     }
     for (long i = done + threadIdx.x; i < len; i += 256) {
         float pp = p[i], mm = m[i], vv = v[i];
-        upd(pp, g[i], mm, vv);
+        upd(pp, g.el(i), mm, vv);
         p[i] = pp, m[i] = mm, v[i] = vv;
     }
 }
@@ -129,15 +192,32 @@ extern "C" int ver_clip_adamw_step(void* const* table, const long* sizes, const 
     if (n_tensors == 0 || n_chunks == 0) return VER_OK;
     VER_REQUIRE(table && sizes && chunk_tensor && chunk_index && partial, VER_EINVAL, "ver_clip_adamw_step: null pointer argument");
     hipStream_t st = (hipStream_t)stream;
+    const TableGrads grads{(const float* const*)table, n_tensors};
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(k_sqnorm, dim3(n_chunks), dim3(256), 0, st, (const float* const*)table, sizes, chunk_tensor, chunk_index,
-                       n_tensors, chunk_elems, partial, (int*)nullptr);
-    hipLaunchKernelGGL(k_clip_adamw, dim3(n_chunks), dim3(256), 0, st, (float* const*)table, sizes, chunk_tensor, chunk_index,
+    hipLaunchKernelGGL(k_sqnorm<TableGrads>, dim3(n_chunks), dim3(256), 0, st, grads, sizes, chunk_tensor, chunk_index,
+                       chunk_elems, partial, (int*)nullptr);
+    hipLaunchKernelGGL(k_clip_adamw<TableGrads>, dim3(n_chunks), dim3(256), 0, st, grads, (float* const*)table, sizes, chunk_tensor, chunk_index,
                        n_tensors, chunk_elems, (const float*)partial, n_chunks, max_norm, lr, beta1, beta2, eps,
                        (float)(1.0 - (double)lr * (double)weight_decay), (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), norm_out,
                        (const float*)nullptr, (const int*)nullptr);
     return ver_check_launch("ver_clip_adamw_step");
 }
+
+namespace {
+// the per-tensor step over any gradient loader: ver_clip_adamw_step_tensors and ver_clip_adamw_step_flat differ in `grads` alone
+template <class Grads>
+int step_tensors(const char* who, const Grads grads, void* const* table, const long* sizes, const int* chunk_tensor,
+                 const int* chunk_index, const float* hyper, int* steps, int n_tensors, int n_chunks, int chunk_elems,
+                 float* partial, float* norm_out, float max_norm, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_sqnorm<Grads>, dim3(n_chunks), dim3(256), 0, st, grads, sizes, chunk_tensor, chunk_index, chunk_elems,
+                       partial, steps);
+    hipLaunchKernelGGL(k_clip_adamw<Grads>, dim3(n_chunks), dim3(256), 0, st, grads, (float* const*)table, sizes, chunk_tensor,
+                       chunk_index, n_tensors, chunk_elems, (const float*)partial, n_chunks, max_norm, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f,
+                       1.f, norm_out, hyper, (const int*)steps);
+    return ver_check_launch(who);
+}
+}  // namespace
 
 extern "C" int ver_clip_adamw_step_tensors(void* const* table, const long* sizes, const int* chunk_tensor, const int* chunk_index,
                                            const float* hyper, int* steps, int n_tensors, int n_chunks, int chunk_elems,
@@ -147,11 +227,85 @@ extern "C" int ver_clip_adamw_step_tensors(void* const* table, const long* sizes
     if (n_tensors == 0 || n_chunks == 0) return VER_OK;
     VER_REQUIRE(table && sizes && chunk_tensor && chunk_index && partial && hyper && steps, VER_EINVAL,
                 "ver_clip_adamw_step_tensors: null pointer argument");
+    return step_tensors("ver_clip_adamw_step_tensors", TableGrads{(const float* const*)table, n_tensors}, table, sizes, chunk_tensor,
+                        chunk_index, hyper, steps, n_tensors, n_chunks, chunk_elems, partial, norm_out, max_norm, stream);
+}
+
+extern "C" int ver_clip_adamw_step_flat(void* const* table, const long* sizes, const long* offsets, const int* chunk_tensor,
+                                        const int* chunk_index, const float* hyper, int* steps, const void* flat, int flat_dtype,
+                                        int n_tensors, int n_chunks, int chunk_elems, float* partial, float* norm_out,
+                                        float max_norm, void* stream) {
+    const char* who = "ver_clip_adamw_step_flat";
+    VER_REQUIRE(n_tensors >= 0 && n_chunks >= 0 && chunk_elems > 0 && chunk_elems % 4 == 0, VER_EINVAL,
+                "%s: bad sizes (%d tensors, %d chunks of %d)", who, n_tensors, n_chunks, chunk_elems);
+    VER_REQUIRE(flat_dtype == VER_F32 || flat_dtype == VER_BF16, VER_EINVAL, "%s: flat_dtype %d (VER_F32 or VER_BF16)", who, flat_dtype);
+    if (n_tensors == 0 || n_chunks == 0) return VER_OK;
+    VER_REQUIRE(table && sizes && offsets && chunk_tensor && chunk_index && partial && hyper && steps && flat, VER_EINVAL,
+                "%s: null pointer argument", who);
+    VER_REQUIRE((reinterpret_cast<uintptr_t>(flat) & 15) == 0, VER_EINVAL, "%s: flat must be 16-byte aligned", who);
+    if (flat_dtype == VER_F32)
+        return step_tensors(who, FlatGradsF32{(const float*)flat, offsets}, table, sizes, chunk_tensor, chunk_index, hyper, steps,
+                            n_tensors, n_chunks, chunk_elems, partial, norm_out, max_norm, stream);
+    return step_tensors(who, FlatGradsBF16{(const unsigned short*)flat, offsets}, table, sizes, chunk_tensor, chunk_index, hyper,
+                        steps, n_tensors, n_chunks, chunk_elems, partial, norm_out, max_norm, stream);
+}
+
+// ver_grad_pack: flat[offsets[t] + i] = g_t[i] * scale, one workgroup per chunk of the optimizer's chunk tables.  A streaming
+// copy (4 bytes read, 4 or 2 written per element): every lane moves 16 bytes per store -- one float4 load for an fp32 wire, two
+// for eight bf16 -- when the gradient and the destination of the chunk are both 16-byte aligned; a gradient that is a view 4 or
+// 8 bytes off (a bucket view) goes element by element, as in k_sqnorm.  Elements between the tensors are not touched.
+template <class T> struct Wire;
+template <> struct Wire<float> {
+    static constexpr int W = 4;
+    __device__ static float one(float f) { return f; }
+    __device__ static void store(float* dst, long i, const float* g, float scale) {
+        const float4 q = reinterpret_cast<const float4*>(g)[i];
+        reinterpret_cast<float4*>(dst)[i] = make_float4(q.x * scale, q.y * scale, q.z * scale, q.w * scale);
+    }
+};
+template <> struct Wire<unsigned short> {
+    static constexpr int W = 8;
+    __device__ static unsigned short one(float f) { return bf16_round(f); }
+    __device__ static void store(unsigned short* dst, long i, const float* g, float scale) {
+        const float4 a = reinterpret_cast<const float4*>(g)[2 * i], b = reinterpret_cast<const float4*>(g)[2 * i + 1];
+        auto two = [&](float lo, float hi) { return (unsigned)bf16_round(lo * scale) | ((unsigned)bf16_round(hi * scale) << 16); };
+        reinterpret_cast<uint4*>(dst)[i] = make_uint4(two(a.x, a.y), two(a.z, a.w), two(b.x, b.y), two(b.z, b.w));
+    }
+};
+
+template <class T>
+__global__ __launch_bounds__(256) void k_grad_pack(const float* const* __restrict__ table, const long* __restrict__ sizes,
+                                                   const long* __restrict__ offsets, const int* __restrict__ chunk_tensor,
+                                                   const int* __restrict__ chunk_index, int chunk, float scale, T* __restrict__ flat) {
+    const int t = chunk_tensor[blockIdx.x];
+    const long start = (long)chunk_index[blockIdx.x] * chunk;
+    const long len = min((long)chunk, sizes[t] - start);
+    const float* g = table[t] + start;
+    T* dst = flat + offsets[t] + start;
+    long done = 0;
+    if (((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
+        const long nv = len / Wire<T>::W;
+        for (long i = threadIdx.x; i < nv; i += 256) Wire<T>::store(dst, i, g, scale);
+        done = nv * Wire<T>::W;
+    }
+    for (long i = done + threadIdx.x; i < len; i += 256) dst[i] = Wire<T>::one(g[i] * scale);
+}
+
+extern "C" int ver_grad_pack(const void* const* table, const long* sizes, const long* offsets, const int* chunk_tensor,
+                             const int* chunk_index, int n_tensors, int n_chunks, int chunk_elems, float scale, void* flat,
+                             int flat_dtype, void* stream) {
+    VER_REQUIRE(n_tensors >= 0 && n_chunks >= 0 && chunk_elems > 0 && chunk_elems % 4 == 0, VER_EINVAL,
+                "ver_grad_pack: bad sizes (%d tensors, %d chunks of %d)", n_tensors, n_chunks, chunk_elems);
+    VER_REQUIRE(flat_dtype == VER_F32 || flat_dtype == VER_BF16, VER_EINVAL, "ver_grad_pack: flat_dtype %d (VER_F32 or VER_BF16)", flat_dtype);
+    if (n_tensors == 0 || n_chunks == 0) return VER_OK;
+    VER_REQUIRE(table && sizes && offsets && chunk_tensor && chunk_index && flat, VER_EINVAL, "ver_grad_pack: null pointer argument");
+    VER_REQUIRE((reinterpret_cast<uintptr_t>(flat) & 15) == 0, VER_EINVAL, "ver_grad_pack: flat must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_sqnorm, dim3(n_chunks), dim3(256), 0, st, (const float* const*)table, sizes, chunk_tensor, chunk_index,
-                       n_tensors, chunk_elems, partial, steps);
-    hipLaunchKernelGGL(k_clip_adamw, dim3(n_chunks), dim3(256), 0, st, (float* const*)table, sizes, chunk_tensor, chunk_index,
-                       n_tensors, chunk_elems, (const float*)partial, n_chunks, max_norm, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 1.f, norm_out,
-                       hyper, (const int*)steps);
-    return ver_check_launch("ver_clip_adamw_step_tensors");
+    if (flat_dtype == VER_F32)
+        hipLaunchKernelGGL(k_grad_pack<float>, dim3(n_chunks), dim3(256), 0, st, (const float* const*)table, sizes, offsets,
+                           chunk_tensor, chunk_index, chunk_elems, scale, (float*)flat);
+    else
+        hipLaunchKernelGGL(k_grad_pack<unsigned short>, dim3(n_chunks), dim3(256), 0, st, (const float* const*)table, sizes, offsets,
+                           chunk_tensor, chunk_index, chunk_elems, scale, (unsigned short*)flat);
+    return ver_check_launch("ver_grad_pack");
 }

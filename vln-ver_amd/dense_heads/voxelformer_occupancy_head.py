@@ -1229,7 +1229,13 @@ class VoxelFormerOccupancyHead(BaseModule):
         with torch.no_grad():
             cost = det_costs(all_cls, all_box, tables, c.weight, c.alpha, c.gamma, c.eps, a.reg_cost.weight)
             match = lsa_solve(cost, gts.counts[None].expand(nl, bs), bad=flag.dev)
-            norm = self._device_normalisers((match >= 0).sum((1, 2)), bs * nq)
+            # (``preset_normalisers``: set by ``graphs.GraphedTrainStep(exchange=)`` around its capture alone -- the static
+            #  [2, L] rows it fills before every replay, because the all-reduce below cannot be captured)
+            norm = getattr(self, 'preset_normalisers', None) if all_cls is not None else None
+            if norm is None:
+                norm = self._device_normalisers((match >= 0).sum((1, 2)), bs * nq)
+            elif tuple(norm.shape) != (2, nl):
+                raise ValueError('preset_normalisers %s for %d decoder layers' % (tuple(norm.shape), nl))
         loss_cls, loss_box, _ = det_set_loss(all_cls, all_box, match, tables, self.code_weights, norm,
                                              (self.loss_cls.loss_weight, loss_box_module.loss_weight), self.loss_cls.alpha,
                                              self.loss_cls.gamma, bad=flag.dev)

@@ -1,5 +1,6 @@
 """hipGraph replay of the head (``GraphedHead``), of the whole lifting step (``GraphedLiftStep``) and of the whole multi-task
-training step with fresh ground truth per replay (``GraphedTrainStep``) for small, launch-bound batches.
+training step with fresh ground truth per replay (``GraphedTrainStep``) for small, launch-bound batches; both steps also
+under data parallelism, as two graphs around one eager all-reduce of a flat gradient buffer (``exchange=``).
 
 At the reference's own batch point (vocc.py: ``samples_per_gpu=1``) the full multi-task step is bound by the HOST: ~1 500
 module calls forward and as many autograd nodes backward, 13-16 ms + 23-28 ms of Python / dispatcher time around ~20 ms of
@@ -101,6 +102,23 @@ class GraphedHead:
                     flow_preds=None, enc_cls_scores=None, enc_bbox_preds=None, enc_occupancy_preds=None)
 
 
+def _check_exchange(who, optimizer, exchange):
+    """An exchange for a captured step covers exactly the optimizer's trainable parameters (the order is the exchange's)."""
+    mine = {id(p) for group in optimizer.param_groups for p in group['params'] if p.requires_grad}
+    theirs = {id(p) for p in exchange.params}
+    if mine != theirs:
+        raise ValueError('%s: the exchange lists %d parameters, the optimizer trains %d, %d in common; the captured update '
+                         'reads every gradient from the exchange, so the two lists must hold the same parameters'
+                         % (who, len(theirs), len(mine), len(mine & theirs)))
+
+
+def _exchanged_update(optimizer, exchange):
+    """The eager tail of a data-parallel step: pack, ONE all-reduce, clipped AdamW from the flat buffer -> clip norm."""
+    exchange.pack()
+    exchange.all_reduce()
+    return optimizer.step(exchange=exchange)
+
+
 class GraphedLiftStep:
     """One training step of the lifting path -- forward, occupancy loss, backward, gradient clipping + AdamW -- for ONE fixed
     batch shape, captured as a single hipGraph and replayed: the reference's own operating point (vocc.py:222
@@ -122,14 +140,25 @@ class GraphedLiftStep:
     heuristics) before the capture -- they train the model like any other step.  One rank only: the gradient all-reduce of
     DistributedDataParallel is not part of the graph.  ``loss = step(feats, w2p, org, gt)`` copies the inputs into the graph's
     static buffers (unless they ARE those buffers: ``step.inputs``) and returns the graph's loss tensor, overwritten by the
-    next call."""
+    next call.
 
-    def __init__(self, model, optimizer, feats, world2pixel, origin, gt, warmup=3, check_live_losses=True):
+    ``exchange``: a ``ddp.GradExchange`` over the optimizer's trainable parameters -- the step under data parallelism, with
+    no DistributedDataParallel wrapper around the model.  Construction first broadcasts rank 0's parameters (when a process
+    group exists); the warm-up steps are eager exchanged steps (backward, ``exchange.pack()``, ``exchange.all_reduce()``,
+    ``optimizer.step(exchange)``); then TWO graphs are captured on one stream, the second in the memory pool of the first:
+    A = forward + loss + backward + ``exchange.pack()``, B = ``optimizer.step(exchange)``.  A call replays A, all-reduces the
+    ONE flat buffer eagerly (the collective is not part of a graph) and replays B.  Without a process group the all-reduce
+    is nothing and the scale is 1: the same two graphs on one rank."""
+
+    def __init__(self, model, optimizer, feats, world2pixel, origin, gt, warmup=3, check_live_losses=True, exchange=None):
         if not feats.is_cuda:
             raise RuntimeError('GraphedLiftStep needs GPU tensors (HIP graphs)')
         if not hasattr(optimizer, 'prepare_capture'):
             raise TypeError('GraphedLiftStep needs an optimizer whose step() can be captured (optim.ClipAdamW)')
-        self.model, self.optimizer = model, optimizer
+        self.model, self.optimizer, self.exchange = model, optimizer, exchange
+        if exchange is not None:
+            _check_exchange('GraphedLiftStep', optimizer, exchange)
+            exchange.broadcast_parameters()
         self.inputs = tuple(t.detach().clone() for t in (feats, world2pixel, origin, gt))
         self.training = model.training
         side = torch.cuda.Stream()
@@ -140,7 +169,7 @@ class GraphedLiftStep:
                 optimizer.zero_grad(set_to_none=True)
                 loss = model(*self.inputs)
                 loss.backward()
-                norm = optimizer.step()
+                norm = optimizer.step() if exchange is None else _exchanged_update(optimizer, exchange)
             self._clean_warmup = norm is not None and bool(torch.isfinite(norm))
             self._unchecked = 3
             loss = None
@@ -155,11 +184,23 @@ class GraphedLiftStep:
                                    'earlier eager steps?); drop them before building the graph (see GraphedHead)' % n)
         optimizer.prepare_capture()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            loss = model(*self.inputs)
-            loss.backward()
-            self.grad_norm = optimizer.step()
-            self.loss = loss.detach()
+        if exchange is None:
+            with torch.cuda.graph(self.graph):
+                loss = model(*self.inputs)
+                loss.backward()
+                self.grad_norm = optimizer.step()
+                self.loss = loss.detach()
+        else:
+            exchange.prepare_capture()
+            stream = torch.cuda.Stream()
+            with torch.cuda.graph(self.graph, stream=stream):
+                loss = model(*self.inputs)
+                loss.backward()
+                exchange.pack()
+                self.loss = loss.detach()
+            self.update_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.update_graph, pool=self.graph.pool(), stream=stream):
+                self.grad_norm = optimizer.step(exchange=exchange)
         loss = None
 
     def __call__(self, feats, world2pixel, origin, gt):
@@ -172,6 +213,10 @@ class GraphedLiftStep:
                 dst.copy_(src, non_blocking=True)
         self.optimizer.refresh()
         self.graph.replay()
+        if self.exchange is not None:
+            self.exchange.all_reduce()
+            self.update_graph.replay()
+            self.exchange.replayed()
         self.optimizer.replayed()
         if self._unchecked:
             # the first replays are checked (one synchronisation each): a replay that leaves a non-finite gradient norm behind
@@ -256,17 +301,30 @@ class GraphedTrainStep:
     ``step.inputs``, ``step.gts``, ``step.occ``) and returns the loss dict: STATIC tensors, overwritten by the next call
     (``float()`` or clone what has to survive it); ``step.total`` is their sum, ``step.grad_norm`` the clip norm.  Refusals are
     decided from sizes the host knows, never from a device read; what only the device knows -- an assignment problem, a pair
-    with a class or voxel out of range, a label outside [0, C] -- is not read in the call: ``flags()`` reads it on demand."""
+    with a class or voxel out of range, a label outside [0, C] -- is not read in the call: ``flags()`` reads it on demand.
+
+    ``exchange``: a ``ddp.GradExchange`` over the optimizer's trainable parameters -- the step under data parallelism, as in
+    ``GraphedLiftStep``: rank 0's parameters broadcast first, eager exchanged warm-up steps, graph A (forward, losses,
+    backward, ``exchange.pack()``) and graph B (``optimizer.step(exchange)``) with the one eager all-reduce between them.  The
+    head's two loss normalisers are all-reduced too, which cannot happen inside graph A; so every call forms them BEFORE
+    the replay, on the device and without a host read: positives per layer = ``clamp(gts.counts, max=Nq).sum()``, through
+    ``head._device_normalisers`` (its all-reduce included) into a static ``[2, L]`` buffer that the captured
+    ``_set_loss_fused`` reads (``head.preset_normalisers``, set for the capture alone) instead of counting matches.  The
+    two agree whenever every assignment problem was solved -- a solved problem matches exactly ``min(Nq, count)`` queries
+    -- which is exactly the case in which ``AssignmentFlag`` stays clear; a flagged problem leaves its queries unmatched
+    while its count still enters the preset normaliser, and ``flags()['assignment']`` reports that case.  A model wrapped
+    in DistributedDataParallel is refused with or without an exchange."""
 
     def __init__(self, model, optimizer, feats, world2pixel, origin, gts, occ, pair_capacity=None, warmup=3,
-                 check_live_losses=True):
+                 check_live_losses=True, exchange=None):
         from .dense_heads.voxelformer_occupancy_head import PaddedGts
         from .hipops import PackedOccGts
         who = 'GraphedTrainStep'
         if isinstance(model, torch.nn.parallel.DistributedDataParallel) or \
                 isinstance(getattr(model, 'head', None), torch.nn.parallel.DistributedDataParallel):
-            raise RuntimeError('%s: a DistributedDataParallel model: the gradient all-reduce is not part of the graph (one '
-                               'rank only)' % who)
+            raise RuntimeError('%s: a DistributedDataParallel model: its bucket hooks and reducer cannot live inside a capture '
+                               '(one rank only); for data parallelism pass the UNWRAPPED model and `exchange=` '
+                               'ddp.GradExchange(parameters)' % who)
         if not hasattr(optimizer, 'prepare_capture'):
             raise TypeError('%s needs an optimizer whose step() can be captured (optim.ClipAdamW)' % who)
         head = model.head
@@ -282,7 +340,10 @@ class GraphedTrainStep:
         if occ.bs != bs or gts.boxes.shape[0] != bs:
             raise ValueError('%s: %d samples of features, %d of boxes, %d of pairs' % (who, bs, gts.boxes.shape[0], occ.bs))
         self._need_gpu(feats, world2pixel, origin, gts, occ)
-        self.model, self.optimizer = model, optimizer
+        self.model, self.optimizer, self.exchange = model, optimizer, exchange
+        if exchange is not None:
+            _check_exchange(who, optimizer, exchange)
+            exchange.broadcast_parameters()
         self.capacity, self.pair_capacity = int(gts.boxes.shape[1]), pair_capacity
         self.inputs = tuple(t.detach().clone() for t in (feats, world2pixel, origin))
         self.gts = PaddedGts(*(t.detach().clone() for t in gts))
@@ -296,11 +357,16 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             norm = None
+            shapes = []                                     # [L, B, Nq, C] of the class scores, for the preset normalisers
+            hook = exchange is not None and head.register_forward_hook(
+                lambda mod, args, kwargs, outs: shapes.append(tuple(outs['all_cls_scores'].shape)), with_kwargs=True)
             for _ in range(max(1, warmup)):                 # (at least one: the optimizer state must exist before the capture)
                 optimizer.zero_grad(set_to_none=True)
                 total = sum(model(*static).values())
                 total.backward()
-                norm = optimizer.step()
+                norm = optimizer.step() if exchange is None else _exchanged_update(optimizer, exchange)
+            if hook:
+                hook.remove()
             self._clean_warmup = norm is not None and bool(torch.isfinite(norm))
             self._unchecked = 3
             total = None
@@ -315,13 +381,34 @@ class GraphedTrainStep:
                                    'steps?); drop them before building the graph (see GraphedHead)' % (who, n))
         optimizer.prepare_capture()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            losses = model(*static)
-            total = sum(losses.values())
-            total.backward()
-            self.grad_norm = optimizer.step()
-            self.losses = {k: v.detach() for k, v in losses.items()}
-            self.total = total.detach()
+        if exchange is None:
+            with torch.cuda.graph(self.graph):
+                losses = model(*static)
+                total = sum(losses.values())
+                total.backward()
+                self.grad_norm = optimizer.step()
+                self.losses = {k: v.detach() for k, v in losses.items()}
+                self.total = total.detach()
+        else:
+            self._layers, self._queries = shapes[0][0], shapes[0][2]
+            self._normalisers = torch.ones(2, self._layers, dtype=torch.float32, device=feats.device)
+            self._load_normalisers()
+            exchange.prepare_capture()
+            stream = torch.cuda.Stream()
+            head.preset_normalisers = self._normalisers
+            try:
+                with torch.cuda.graph(self.graph, stream=stream):
+                    losses = model(*static)
+                    total = sum(losses.values())
+                    total.backward()
+                    exchange.pack()
+                    self.losses = {k: v.detach() for k, v in losses.items()}
+                    self.total = total.detach()
+            finally:
+                head.preset_normalisers = None
+            self.update_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.update_graph, pool=self.graph.pool(), stream=stream):
+                self.grad_norm = optimizer.step(exchange=exchange)
         self._targets = model.targets                      # the capture's OccupancyTargets: static tensors the replays rewrite
         losses = total = None
 
@@ -370,6 +457,15 @@ class GraphedTrainStep:
             self.occ.offsets.copy_(occ.offsets, non_blocking=True)
             self.occ.pairs[:occ.n_total].copy_(occ.pairs, non_blocking=True)
 
+    @torch.no_grad()
+    def _load_normalisers(self):
+        """The two loss normalisers of the step whose counts sit in ``self.gts``, into the static buffer graph A reads: eager
+        device work (and, with a process group, the head's one all-reduce), no host read."""
+        head = self.model.head
+        bs = self.gts.counts.shape[0]
+        positives = self.gts.counts.clamp(max=self._queries).sum().to(torch.int64).expand(self._layers)
+        self._normalisers.copy_(head._device_normalisers(positives, bs * self._queries))
+
     def __call__(self, feats, world2pixel, origin, gts, occ):
         who = 'GraphedTrainStep'
         if self.model.training != self.training:
@@ -386,7 +482,14 @@ class GraphedTrainStep:
                 dst.copy_(src, non_blocking=True)
         self._load_gts(gts, occ)
         self.optimizer.refresh()
-        self.graph.replay()
+        if self.exchange is None:
+            self.graph.replay()
+        else:
+            self._load_normalisers()
+            self.graph.replay()
+            self.exchange.all_reduce()
+            self.update_graph.replay()
+            self.exchange.replayed()
         self.optimizer.replayed()
         if self._unchecked:
             # as GraphedLiftStep: the first replays are checked (one synchronisation each) for the runtime's memset-node problem

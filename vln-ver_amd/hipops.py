@@ -1348,6 +1348,24 @@ def dropout_keep_host(indices, seed, p_drop):
     return (h & np.uint64(0xffffff)) < thresh
 
 
+def pack_host(grad, scale, wire_dtype=torch.float32):
+    """``ver_grad_pack``'s arithmetic on one gradient in numpy (csrc/ver_optim.hip bf16_round): the fp32 product
+    ``grad * scale``; for a bf16 wire rounded once to nearest-even on the bit pattern -- a NaN becomes the quiet NaN
+    0x7fc0, +-inf stay, a finite product past the largest bf16 rounds to +-inf.  -> float32 array (fp32 wire) or the
+    uint16 bit patterns (bf16 wire), flat."""
+    import numpy as np
+    g = np.ascontiguousarray(np.asarray(grad, dtype=np.float32)).reshape(-1)
+    with np.errstate(over='ignore', invalid='ignore', under='ignore'):
+        prod = (g * np.float32(scale)).astype(np.float32)
+    if wire_dtype == torch.float32:
+        return prod
+    if wire_dtype != torch.bfloat16:
+        raise TypeError('pack_host: wire dtype float32 or bfloat16, got %s' % (wire_dtype,))
+    u = prod.view(np.uint32).astype(np.uint64)
+    rounded = ((u + np.uint64(0x7fff) + ((u >> np.uint64(16)) & np.uint64(1))) >> np.uint64(16)).astype(np.uint16)
+    return np.where((u & np.uint64(0x7fffffff)) > np.uint64(0x7f800000), np.uint16(0x7fc0), rounded)
+
+
 def _row_pitch(t):
     """(t or a contiguous copy of it, elements between consecutive rows of its flattened leading dimensions): a [N, B, C]
     view with last-dimension stride 1 and a uniform row pitch (a column slice of a wider GEMM output) goes as it is."""

@@ -2,7 +2,9 @@
 (projects/configs/verformer/vocc.py:260-274: ``optimizer=dict(type='AdamW', ..., paramwise_cfg=...)``,
 ``optimizer_config=dict(grad_clip=dict(max_norm=..., norm_type=2))``, run by mmcv's OptimizerHook as ``clip_grad_norm_`` +
 ``optimizer.step()``) -- as ONE C-ABI call over all parameters: ``ver_clip_adamw_step_tensors`` (csrc/ver_optim.hip; two
-launches, 32 bytes per parameter).
+launches, 32 bytes per parameter).  ``step(exchange)`` is the same update with the gradients read from the flat buffer of a
+``ddp.GradExchange`` (``ver_clip_adamw_step_flat``; fp32 or bf16 on the wire) -- data-parallel steps without a
+DistributedDataParallel wrapper, bit for bit the update ``step()`` applies to fp32 gradient tensors of the same values.
 
 ``ClipAdamW`` keeps torch.optim.AdamW's state layout (``exp_avg`` / ``exp_avg_sq`` / ``step`` per parameter) and arithmetic
 (decoupled weight decay, bias corrections from the PARAMETER's own step count, amsgrad off).  Any number of parameter groups
@@ -66,11 +68,14 @@ class ClipAdamW(torch.optim.Optimizer):
                 self._tables.pop(next(iter(self._tables)))
         return hit
 
-    def _collect(self):
+    def _collect(self, exchange=None):
         """-> (parameters with a gradient, their gradients, hyper rows [n][6], max_norm): state created on first sight, ``step``
-        normalised to an int (a torch AdamW checkpoint holds one tensor per parameter)."""
+        normalised to an int (a torch AdamW checkpoint holds one tensor per parameter).  With an exchange: its parameter
+        list in ITS order (the order of the flat buffer), every one of which must be ours; ``p.grad`` is not looked at and no
+        gradients are returned."""
         ps, gs, hyper = [], [], []
         max_norm = None
+        rows = {}
         for group in self.param_groups:
             mn = float(group.get('max_norm') or 0.0)
             if max_norm is None:
@@ -82,6 +87,9 @@ class ClipAdamW(torch.optim.Optimizer):
                 raise ValueError('ClipAdamW: hyper-parameters out of range in a parameter group')
             row = (float(group['lr']), float(b1), float(b2), float(group['eps']), float(group['weight_decay']), 0.0)
             for p in group['params']:
+                if exchange is not None:
+                    rows[id(p)] = row
+                    continue
                 g = p.grad
                 if g is None:
                     continue
@@ -97,6 +105,19 @@ class ClipAdamW(torch.optim.Optimizer):
                 ps.append(p)
                 gs.append(g if g.is_contiguous() else g.contiguous())
                 hyper.append(row)
+        if exchange is not None:
+            for k, p in zip(exchange.names, exchange.params):
+                if id(p) not in rows:
+                    raise ValueError('ClipAdamW.step(exchange): %s of the exchange is not a parameter of this optimizer' % k)
+                st = self.state[p]
+                if not st:
+                    st['step'] = 0
+                    st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                elif not isinstance(st['step'], int):
+                    st['step'] = int(st['step'])
+                ps.append(p)
+                hyper.append(rows[id(p)])
         return ps, gs, hyper, max_norm or 0.0
 
     def _upload(self, ptrs, hyper, steps, dev, capturing):
@@ -147,20 +168,33 @@ class ClipAdamW(torch.optim.Optimizer):
 
     # ------------------------------------------------------------------ the step
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, exchange=None):
         """One clipped AdamW update of every parameter that has a gradient.  Returns the gradient norm before clipping
-        (a device scalar, like ``clip_grad_norm_``)."""
+        (a device scalar, like ``clip_grad_norm_``).
+
+        ``exchange``: a ``ddp.GradExchange`` -- the update of ITS parameter list (all of them parameters of this optimizer)
+        from the gradients in its flat buffer, as ``pack()`` and ``all_reduce()`` left them; ``p.grad`` is not consulted.
+        Capture support is the same: ``prepare_capture``, ``replayed``, ``refresh`` and the invalidation rules above."""
+        from . import hipops
+        from .ddp import GradExchange
+        if exchange is None and isinstance(closure, GradExchange):         # ``step(exchange)``
+            closure, exchange = None, closure
         if closure is not None:
             raise NotImplementedError('ClipAdamW: no closure')
-        from . import hipops
-        ps, gs, hyper, max_norm = self._collect()
+        if exchange is not None and not isinstance(exchange, GradExchange):
+            raise TypeError('ClipAdamW.step(exchange): a ddp.GradExchange, got %s' % type(exchange).__name__)
+        ps, gs, hyper, max_norm = self._collect(exchange)
         if not ps:
             return torch.zeros(())
         dev = ps[0].device
         capturing = torch.cuda.is_current_stream_capturing()
         n = len(ps)
         states = [self.state[p] for p in ps]
-        ptrs = ([p.data_ptr() for p in ps] + [g.data_ptr() for g in gs] + [st['exp_avg'].data_ptr() for st in states]
+        if exchange is not None:
+            if exchange.device != dev or exchange.chunk != self.CHUNK:
+                raise ValueError('ClipAdamW.step(exchange): the exchange lives on %s with chunks of %d' % (exchange.device, exchange.chunk))
+            gs = [None] * n                                # (the gradient row of the table is not read: zeros)
+        ptrs = ([p.data_ptr() for p in ps] + [0 if g is None else g.data_ptr() for g in gs] + [st['exp_avg'].data_ptr() for st in states]
                 + [st['exp_avg_sq'].data_ptr() for st in states])
         steps = [st['step'] for st in states]
         if not capturing and self._captured and [id(st) for st in states] != [id(st) for st in self._captured]:
@@ -170,14 +204,21 @@ class ClipAdamW(torch.optim.Optimizer):
         tables = self._chunk_tables([p.numel() for p in ps], dev)
         sizes, chunk_tensor, chunk_index, partial = tables
         L = hipops.lib()
-        hipops._launch('ver_clip_adamw_step', lambda: L.ver_clip_adamw_step_tensors(
-            hipops._p(d['table']), hipops._p(sizes), hipops._p(chunk_tensor), hipops._p(chunk_index), hipops._p(d['hyper_dev']),
-            hipops._p(d['steps_dev']), n, chunk_tensor.numel(), self.CHUNK, hipops._p(partial), hipops._p(norm), max_norm,
-            hipops._stream()))
+        if exchange is None:
+            hipops._launch('ver_clip_adamw_step', lambda: L.ver_clip_adamw_step_tensors(
+                hipops._p(d['table']), hipops._p(sizes), hipops._p(chunk_tensor), hipops._p(chunk_index), hipops._p(d['hyper_dev']),
+                hipops._p(d['steps_dev']), n, chunk_tensor.numel(), self.CHUNK, hipops._p(partial), hipops._p(norm), max_norm,
+                hipops._stream()))
+        else:
+            hipops._launch('ver_clip_adamw_step', lambda: L.ver_clip_adamw_step_flat(
+                hipops._p(d['table']), hipops._p(sizes), hipops._p(exchange.offsets_dev), hipops._p(chunk_tensor),
+                hipops._p(chunk_index), hipops._p(d['hyper_dev']), hipops._p(d['steps_dev']), hipops._p(exchange.flat),
+                1 if exchange.wire_dtype == torch.bfloat16 else 0, n, chunk_tensor.numel(), self.CHUNK, hipops._p(partial),
+                hipops._p(norm), max_norm, hipops._stream()))
         if capturing:
             # nothing has run: the replays advance the device counts, ``replayed()`` the host's
             self._captured, self._stale = states, None
-            self._keep.append((d['table'], d['hyper_dev'], d['steps_dev'], tables))
+            self._keep.append((d['table'], d['hyper_dev'], d['steps_dev'], tables, exchange))
         else:
             for st in states:
                 st['step'] += 1
