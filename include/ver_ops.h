@@ -252,6 +252,8 @@ int ver_lattice_col2im(const void* grad_col, void* grad_src, const int* taps, in
  *   (2y'+pm, 2x'+pn) of the combined (H, W) lattice      2 z-split [B,2,H,W,2,C] (Zs = 4): element
  *   (b,z,y,x) at row (b, z&1, y, x), channel block z>>1      3 planar z-split: four planes of layout 2.
  * scatter is the adjoint (gather form, no atomics): grad_src is overwritten in the source's layout.
+ * Limits: the gather takes any C (whole 16-byte vectors); the scatter gives a lane one 16-byte vector of one position and
+ * REFUSES (VER_EUNSUPPORTED) more than 256 vectors per position, C > 2048 bf16 / 1024 f32 channels.
  */
 /* const_rows (may be NULL): [Zr*H*W][const_blocks][const_width] elements, the constant-pattern blocks of one viewpoint's
  * rows; the gather copies them to columns const_offset[0 .. const_blocks) of every viewpoint (whole 16-byte vectors).
@@ -269,7 +271,10 @@ int ver_lattice_scatter(const void* grad_col, void* grad_src, const int* taps, c
  *       weight[.., 2-a, 4-b, 4-c];  _backward: gradient of the taps -> f32 gradient of the weight.
  *   ver_lattice_transpose    : even lattice channels-last (one of the four layouts of
  *       ver_lattice_gather) <-> channel-first rows cf[b*cf_stride + ((c*Z + z)*H + y)*W + x]
- *       (to_channel_first != 0: channels_last is read; else it is written).
+ *       (to_channel_first != 0: channels_last is read; else it is written).  Any C, cf_stride >= C Z H W and alignment of
+ *       the element type are taken (16-byte channel vectors and 8-byte position vectors where everything is whole and
+ *       aligned, element by element otherwise); a row of 128 channels x (W + 1) positions must fit 64 KB of LDS: W <= 255
+ *       bf16, W <= 127 f32, wider lattices are REFUSED (VER_EUNSUPPORTED).
  */
 int ver_convt_weight_forward(const float* weight, void* taps, long pairs, int dtype, void* stream);
 int ver_convt_weight_backward(const void* grad_taps, float* grad_weight, long pairs, int dtype, void* stream);
@@ -305,7 +310,10 @@ int ver_lattice_transpose(void* channels_last, void* channel_first, long cf_stri
  *       raw .view (head:564) tile the flat channel-first lattice periodically: flat = k*quarter + row*period + off, the
  *       segment j with seg_off[j] <= off < seg_off[j] + seg_len[j] (host tables, nseg <= 8, the segments cover the
  *       period in order) is a pattern group whose rows live at rows[seg_base[j] + (b*seg_rows[j] + row)*seg_pitch[j]
- *       + k*seg_len[j] + (off - seg_off[j])] (elements).  to_rows != 0: the lattice is read; else it is written. */
+ *       + k*seg_len[j] + (off - seg_off[j])] (elements).  to_rows != 0: the lattice is read; else it is written.
+ *       Limits (refused otherwise): period <= 4096, a multiple of 4 like every seg_len / seg_pitch / seg_base; quarter a
+ *       multiple of period and of H*W and a divisor of C Z H W; seg_rows[j] * period == quarter; seg_pitch[j] >=
+ *       (C Z H W / quarter) * seg_len[j]; W % 4 == 0, C % 8 == 0, W <= 252; the lattice below 2^31 elements. */
 int ver_lattice_rows(void* channels_last, void* rows, long quarter, int period, int nseg, const int* seg_off,
                      const int* seg_len, const long* seg_base, const int* seg_pitch, const int* seg_rows, int B, int Z,
                      int H, int W, int C, int layout, int to_rows, int dtype, void* stream);
