@@ -1017,6 +1017,38 @@ int ver_mha_backward(const void* q, const void* k, const void* v, int dtype, lon
                      void* grad_v, long ldgq, long ldgk, long ldgv, int B, int heads, int head_dim, int Nq, int Nk,
                      void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Occupancy pairs from byte labels (additive to ABI 31; csrc/ver_pairs.hip): the inverse of ver_occ_targets, and the tail of
+ * VoxelFormerOccupancyHead.get_occupancy_prediction (head:1535-1540: idx = where(cls < C); stack(idx, cls[idx])) in fixed
+ * shapes -- the class bytes of a batch become per-sample sparse (voxel index, class) pairs with offsets, the layout
+ * ver_occ_targets takes, without a host read of the pair count.
+ *   labels       u8 [bs * voxel_num]: with row_table == NULL in the reference's (Z, X, Y) voxel order (byte b * voxel_num + v);
+ *                with a table in the group-major row order of the occupancy GEMMs, the byte of (sample b, voxel v) being where
+ *                ver_occ_targets puts it (see there).  A table entry that points outside the buffer reads as empty.
+ *   row_table    i32 [voxel_num / zdim][3] or NULL, as for ver_occ_targets
+ *   pairs        i32 | i64 [capacity][2] (pair_dtype = VER_I32 | VER_I64; aligned to one pair; may be NULL when capacity == 0):
+ *                (voxel index within the sample, class) of every occupied voxel, ascending within a sample, sample after
+ *                sample.  Only the first min(total, capacity) pairs are written; what lies behind them is left as it was.
+ *   offsets      i32 [bs + 1], written: exclusive prefix sums of the per-sample counts, each clamped to `capacity` -- sample b
+ *                owns pairs [offsets[b], offsets[b+1]), and no slice reaches past the buffer
+ *   count        i32 [bs + 2], written: the true occupied count of every sample, their true total, then 1 when the total
+ *                exceeded `capacity` and 0 when not (written, not ORed)
+ *   block_work   i32 [ver_occ_pairs_blocks(bs, voxel_num)] scratch; a workgroup covers ver_occ_pairs_block_size() consecutive
+ *                voxels of one sample
+ *   flags        bit 0: add b * voxel_num to the voxel index -- the index over the flattened batch
+ * A byte < classes is an occupied voxel; `classes` (empty) and anything above (255 = invalid) produce nothing.  Integer
+ * results: bit-exact.  Three launches (block counts, one scan, ordered compaction), plain vector stores, no memset node, no
+ * allocation, no host read: the call can be captured.  bs == 0 or voxel_num == 0: VER_OK, nothing is launched and no pointer
+ * is looked at.  Supported: bs * voxel_num < 2^31 (so flattened indices fit int32 pairs too), classes < 255,
+ * voxel_num % zdim == 0, bs < 65 536, capacity < 2^31 (VER_EUNSUPPORTED beyond); negative sizes, zdim < 1, classes < 1, an
+ * unknown dtype or flag, a null or misaligned pointer: VER_EINVAL.
+ */
+long ver_occ_pairs_block_size(void);
+long ver_occ_pairs_blocks(int bs, long voxel_num);
+int  ver_occ_pairs(const uint8_t* labels, const int32_t* row_table, void* pairs, int pair_dtype, int32_t* offsets,
+                   int32_t* count, int32_t* block_work, long capacity, long voxel_num, int zdim, int classes, int bs,
+                   int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

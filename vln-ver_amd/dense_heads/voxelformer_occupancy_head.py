@@ -49,6 +49,42 @@ def _mean_over_ranks(value, like):
 # (gravity centre, dims, yaw, zero velocity; rows >= counts[b] are padding), labels int64 [bs, cap], counts int32 [bs].
 PaddedGts = collections.namedtuple('PaddedGts', 'boxes labels counts')
 
+# What ``VoxelFormerOccupancyHead.infer`` returns, all on the device and in shapes that depend on nothing a viewpoint holds:
+# volume [bs, Nq, C] (the encoder output); boxes [bs, K, box_dim] (bottom-centre z), scores [bs, K], labels int32 [bs, K], valid
+# uint8 [bs, K] as ``get_bboxes_padded(fused=True)`` gives them; classes uint8 [bs * voxel_num] in the order of ``plan`` (the
+# GEMMs' row order; None: the reference's voxel order); occ_pairs int32 [capacity, 2] (voxel index within the sample, class),
+# occ_offsets int32 [bs + 1], occ_count int32 [bs + 2] as ``hipops.occ_pairs`` gives them.
+InferenceOutputs = collections.namedtuple('InferenceOutputs', 'volume boxes scores labels valid classes plan occ_pairs occ_offsets occ_count')
+
+
+def inference_results(head, outs, img_metas=None):
+    """``InferenceOutputs`` -> what ``VoxelFormer.simple_test`` returns, ``(volume [Nq, bs, C] on the device, [dict(pts_bbox=
+    dict(boxes_3d, scores_3d, labels_3d))] per sample, dict(occupancy_preds, flow_preds=None))``, with ONE device -> host copy:
+    every table travels as 32-bit words of one buffer and is cut apart on the host.  ``occupancy_preds``: int64 [K_b, 2]
+    (voxel index within the sample, class) per sample -- a list, or for a single viewpoint the reference's single tensor."""
+    bs, k, dim = outs.boxes.shape
+    as_words = lambda t: t.contiguous().view(torch.int32).reshape(-1)
+    parts = [as_words(outs.boxes.float()), as_words(outs.scores.float()), outs.labels.to(torch.int32).reshape(-1),
+             outs.valid.to(torch.int32).reshape(-1), outs.occ_pairs.reshape(-1), outs.occ_offsets, outs.occ_count]
+    sizes = [p.numel() for p in parts]
+    host = torch.cat(parts).cpu()
+    boxes, scores, labels, valid, pairs, offsets, count = host.split(sizes)
+    boxes, scores = boxes.view(torch.float32).view(bs, k, dim), scores.view(torch.float32).view(bs, k)
+    labels, valid, pairs = labels.view(bs, k), valid.view(bs, k), pairs.view(-1, 2)
+    bbox_list = []
+    for b, meta in zip(range(bs), img_metas or [None] * bs):
+        keep = valid[b] != 0
+        box_type = (meta or {}).get('box_type_3d')
+        kept = boxes[b][keep]
+        bbox_list.append(dict(pts_bbox=dict(boxes_3d=box_type(kept, dim) if box_type is not None else kept,
+                                            scores_3d=scores[b][keep], labels_3d=labels[b][keep].long())))
+    if int(count[bs + 1]):
+        raise RuntimeError('inference: %d occupied voxels do not fit the pair capacity %d (pair_capacity=); the pairs '
+                           'behind it were not written' % (int(count[bs]), pairs.shape[0]))
+    off = offsets.tolist()
+    occ = [pairs[off[b]:off[b + 1]].long() for b in range(bs)]
+    return outs.volume.permute(1, 0, 2), bbox_list, dict(occupancy_preds=occ[0] if bs == 1 else occ, flow_preds=None)
+
 
 def _to_device_async(t, dev):
     """Host tensor -> ``dev`` without making the host wait for the stream (pinned staging + asynchronous copy); the
@@ -526,8 +562,7 @@ class VoxelFormerOccupancyHead(BaseModule):
         #  launches per direction do execute beside the occupancy head's GEMMs, but those fill every CU, the small kernels
         #  stretch 2x and the 64-viewpoint step gains 0.7 % (480 -> 483 viewpoints/s); one traced run with the second
         #  stream never finished.  One stream.)
-        with self._detection_params(voxel_embed):
-            out = self._detection_half(voxel_embed, object_query_embeds, targets_for, img_metas, kwargs)
+        out = self.detect_from_volume(voxel_embed, object_query_embeds, targets_for=targets_for, img_metas=img_metas, **kwargs)
         bev_embed, all_cls, all_box, layouts, pending = out
         if self.only_det:
             occupancy = None
@@ -576,6 +611,17 @@ class VoxelFormerOccupancyHead(BaseModule):
             lowp = self.__dict__['_lowp_detection'] = LowpParams([r for r in roots if r is not None])
         on = os.environ.get('VER_LOWP_PARAMS', '1') == '1'            # (0: autocast's own per-call casts, for A/B runs)
         return lowp.lent() if (on and lowp.applies(like)) else contextlib.nullcontext()
+
+    def detect_from_volume(self, voxel_embed, object_query_embeds=None, targets_for=None, img_metas=None, **kwargs):
+        """The detection half of ``forward`` on an encoder output ``voxel_embed`` [bs, Nq, C] (``forward(..., only_bev=True)``):
+        decoder, cls / reg (/ layout) branches and box de-normalisation of every decoder layer, under the lent bf16 parameter
+        copies where they apply -> (bev_embed [Nq, bs, C], all_cls [L, bs, Nq, classes], all_box [L, bs, Nq, code], layouts,
+        pending).  ``object_query_embeds``: None = the head's query embedding in the volume's dtype.  The statements
+        ``forward`` runs between its encoder pass and its occupancy branch, so the two halves can be called one by one."""
+        if object_query_embeds is None:
+            object_query_embeds = self.query_embedding.weight.to(voxel_embed.dtype)
+        with self._detection_params(voxel_embed):
+            return self._detection_half(voxel_embed, object_query_embeds, targets_for, img_metas, kwargs)
 
     def _detection_half(self, voxel_embed, object_query_embeds, targets_for, img_metas, kwargs):
         """Decoder + cls / reg (/ layout) branches on the encoder output [bs,Nq,C] (head:584-613), and the start of the
@@ -953,6 +999,77 @@ class VoxelFormerOccupancyHead(BaseModule):
         flat = classes.reshape(-1)
         occ_index, = torch.where(flat < self.occupancy_classes)
         return torch.stack([occ_index, flat[occ_index].long()], dim=-1)
+
+    # ------------------------------------------------------------------ inference in fixed shapes
+    def _check_infer(self):
+        who = 'VoxelFormerOccupancyHead.infer'
+        if self.training:
+            raise RuntimeError('%s: the head is in training mode; inference runs in eval mode (head.eval())' % who)
+        if self.add_layout:
+            raise NotImplementedError('%s: add_layout=True: the room-layout terms are not part of the captured step' % who)
+        if self.only_occ or self.only_det:
+            raise NotImplementedError('%s covers the default multi-task branch of the head (only_occ / only_det are set)' % who)
+        if getattr(self, 'getbev', None) is not None:
+            raise NotImplementedError('%s: a head built with getbev=<store> writes volumes to the host inside forward (device '
+                                      '-> host copies and file I/O), which cannot be captured' % who)
+
+    def _infer_classes(self, voxel_embed, occ_threshold):
+        """(class bytes uint8 [bs * voxel_num], plan): in the GEMMs' row order of ``plan`` where the head takes the lattice
+        path -- from the classifying MLP launch without logits where ``_fused_eval_rows`` applies, from the row-order logits
+        under ``get_occupancy_prediction``'s rule otherwise -- and in the reference's voxel order (plan None) on the dense path."""
+        fused = self._fused_eval_rows(voxel_embed)
+        if fused is not None:
+            from ..hipops import occ_mlp_classes
+            x, plan, _ = fused
+            image, vec, eps = self._fused_eval_params()
+            return occ_mlp_classes(x, image, vec, occ_threshold, eps=eps, first_linear=False, centered=True).reshape(-1), plan
+        preds = self.occupancy_from_volume(voxel_embed, rows_only=True)
+        logits, plan = (preds[0], preds[1]) if isinstance(preds, tuple) else (preds, None)
+        flat = logits.reshape(-1, self.occupancy_classes)
+        if flat.is_cuda and self.occupancy_classes % 8 == 0:
+            from ..hipops import occ_predict_classes
+            return occ_predict_classes(flat, occ_threshold), plan
+        return classify(flat, occ_threshold).to(torch.uint8), plan
+
+    @torch.no_grad()
+    def infer(self, feats, world2pixel, origin, occ_threshold=0.25, pair_capacity=None, autocast_dtype=torch.bfloat16, out=None):
+        """One inference step in fixed shapes and without a host read: feats [Ncam, bs, Nk, C], world2pixel [bs, Ncam, 4, 4],
+        origin [bs, 3] -> ``InferenceOutputs``.  ONE encoder pass; the detection half on its output (``detect_from_volume``)
+        and the fused decode of the last decoder layer (``get_bboxes_padded(fused=True)``); occupancy as class bytes in the
+        GEMMs' row order -- one ``ver_occ_mlp_classes`` launch and no logits under bf16 autocast, the row-order logits
+        classified by ``get_occupancy_prediction``'s kernels in fp32 (``autocast_dtype=None``) -- and ``ver_occ_pairs`` with
+        the plan's row table: per-sample (voxel index, class) pairs with offsets, at most ``pair_capacity`` of them (None:
+        ``bs * voxel_num``, which cannot overflow; ``occ_count[bs + 1]`` reports an overflow).  No logits in voxel order, no
+        permuting copy, no pair count on the host: every call launches the same work, so it can be captured
+        (``graphs.GraphedInference``).  ``out``: the ``InferenceOutputs`` of an earlier call with the same shapes to write
+        into.  Eval mode, the default multi-task branch, no ``getbev``."""
+        from .. import hipops
+        self._check_infer()
+        bs = feats.shape[1]
+        on = autocast_dtype is not None and feats.is_cuda
+        with torch.autocast('cuda', dtype=autocast_dtype or torch.bfloat16, enabled=on, cache_enabled=False):
+            voxel_embed = self.forward(feats, None, only_bev=True, world2pixel=world2pixel, origin=origin)
+            _, all_cls, all_box, _, _ = self.detect_from_volume(voxel_embed, self.query_embedding.weight.to(feats.dtype),
+                                                                world2pixel=world2pixel, origin=origin)
+            decoded = self.get_bboxes_padded(dict(all_cls_scores=all_cls, all_bbox_preds=all_box), fused=True)
+            classes, plan = self._infer_classes(voxel_embed, occ_threshold)
+        z, nc = self.occ_zdim, self.occupancy_classes
+        if out is not None:
+            for dst, src in zip(out[:6], (voxel_embed,) + tuple(decoded) + (classes,)):
+                dst.copy_(src)
+            voxel_embed, decoded, classes = out.volume, tuple(out[1:5]), out.classes
+        if classes.is_cuda:
+            table = row_table(plan, classes.device) if plan is not None else None
+            pairs = hipops.occ_pairs(classes, bs, self.voxel_num, z, nc, table, pair_capacity,
+                                     out=None if out is None else (out.occ_pairs, out.occ_offsets, out.occ_count))
+        else:
+            pairs = tuple(torch.from_numpy(a) for a in hipops.occ_pairs_host(
+                classes.numpy(), bs, self.voxel_num, z, nc, row_table(plan) if plan is not None else None, pair_capacity))
+            if out is not None:
+                for dst, src in zip(out[7:], pairs):
+                    dst.copy_(src)
+                pairs = tuple(out[7:])
+        return InferenceOutputs(voxel_embed, *decoded, classes, plan, *pairs)
 
     def get_occupancy_prediction_from_volume(self, voxel_embed, occ_threshold=0.25):
         """``get_occupancy_prediction`` of ``occupancy_from_volume(voxel_embed)`` -- the same pairs -- through the class map."""

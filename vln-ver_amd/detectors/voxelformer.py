@@ -195,6 +195,8 @@ class VoxelFormer(BaseModule):
         """:349-373 -> (volume, [dict(pts_bbox=...)] per sample, occ_results with the sparse (index, class) pairs)."""
         bbox_list = [dict() for _ in range(len(img_metas))]
         img_feats = self.viewpoint_features(img_metas)
+        if self.device_inference:
+            return self._device_simple_test(img_feats, img_metas, occ_threshold)
         new_prev_bev, bbox_pts, occ_results = self.simple_test_pts(img_feats, img_metas, prev_bev, rescale=rescale)
         if occ_results['occupancy_preds'] is not None:
             occ_results = self.pts_bbox_head.get_occupancy_prediction(occ_results, occ_threshold)
@@ -204,6 +206,21 @@ class VoxelFormer(BaseModule):
             for result_dict, pts_bbox in zip(bbox_list, bbox_pts):
                 result_dict['pts_bbox'] = pts_bbox
         return new_prev_bev, bbox_list, occ_results
+
+    # ``simple_test`` through ``head.infer``: one encoder pass, boxes and per-sample occupancy pairs in fixed shapes on the
+    # device, ONE device -> host copy of all tables.  Off by default: the fused decode orders equal scores by
+    # (query, class) (see ``fused_detection_decode``), ``occupancy_preds`` of a batch is a list of per-sample tensors instead
+    # of one tensor over the flattened batch, and the result dict carries no logits.  ``autocast_dtype`` applies as in training.
+    device_inference = False
+
+    def _device_simple_test(self, img_feats, img_metas, occ_threshold):
+        from ..dense_heads.voxelformer_occupancy_head import inference_results
+        head = self.pts_bbox_head
+        # (the cameras of the metas, through the encoder's caching store: what forward(img_metas) would look up itself)
+        w2p, org = head.transformer.encoder._cameras(len(img_metas), img_feats.device, dict(img_metas=img_metas))
+        lowp = self.autocast_dtype if img_feats.is_cuda else None
+        outs = head.infer(img_feats, w2p, org, occ_threshold=occ_threshold, autocast_dtype=lowp)
+        return inference_results(head, outs, img_metas)
 
     # what ``evaluate_occupancy(fused=None)`` resolves to.  Measured: the fused launch ties with the
     # two-kernel path at one threshold and is 2 % slower at eight, so the default stays on the logits path; ``fused=True``

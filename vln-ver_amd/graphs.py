@@ -1,6 +1,7 @@
 """hipGraph replay of the head (``GraphedHead``), of the whole lifting step (``GraphedLiftStep``) and of the whole multi-task
 training step with fresh ground truth per replay (``GraphedTrainStep``) for small, launch-bound batches; both steps also
-under data parallelism, as two graphs around one eager all-reduce of a flat gradient buffer (``exchange=``).
+under data parallelism, as two graphs around one eager all-reduce of a flat gradient buffer (``exchange=``).  Inference --
+boxes, per-sample occupancy pairs and the volume of a viewpoint -- replays as one graph too (``GraphedInference``).
 
 At the reference's own batch point (vocc.py: ``samples_per_gpu=1``) the full multi-task step is bound by the HOST: ~1 500
 module calls forward and as many autograd nodes backward, 13-16 ms + 23-28 ms of Python / dispatcher time around ~20 ms of
@@ -512,3 +513,90 @@ class GraphedTrainStep:
         dev = self.total.device
         values = torch.cat([AssignmentFlag.of(dev).dev, LabelRangeFlag.of(dev).dev, self._targets.bad]).tolist()
         return dict(zip(('assignment', 'label_range', 'rejected_pairs', 'lost_listings'), values))
+
+
+class GraphedInference:
+    """One inference step of the whole head -- ``head.infer``: encoder, detection decoder, fused box decode, occupancy class
+    bytes and per-sample (voxel, class) pairs -- for one fixed batch shape, captured as a SINGLE hipGraph and replayed: what
+    an agent pays per navigation step at the reference's batch point.  Same kernels, same arithmetic as the eager call; every
+    output has a fixed shape (``InferenceOutputs``: padded box tables with ``valid``, pairs with offsets and counts), so
+    nothing between the inputs and the outputs runs on, or waits for, the host.
+
+    The sample inputs fix every shape: ``feats [Ncam, B, Nk, C]``, ``world2pixel [B, Ncam, 4, 4]``, ``origin [B, 3]`` on the
+    GPU.  ``autocast_dtype``: torch.bfloat16 (default; the occupancy classes come from the classifying MLP launch, no logits)
+    or None = fp32.  ``pair_capacity``: the most occupied voxels of the batch the pair table holds (None: ``B * voxel_num``,
+    which cannot overflow; a smaller table makes the one host copy of ``results()`` smaller, and an overflow is reported in
+    ``occ_count[B + 1]`` and raised by ``results()``).  Construction follows ``GraphedTrainStep``: ``warmup`` eager calls on a
+    side stream (library handles, the row plan and its table, the packed MLP image are built there and never under capture),
+    then one capture of ``head.infer`` on one stream.
+
+    ``outs = step(feats, w2p, origin)`` checks shapes and dtypes on the host, copies the inputs into the static buffers
+    (unless they ARE those buffers: ``step.inputs``), replays and returns the STATIC ``InferenceOutputs``, overwritten by the
+    next call.  ``step.results(img_metas=None)`` makes the single device -> host copy and returns what
+    ``VoxelFormer.simple_test`` returns (``inference_results``).  The head must be in eval mode, at capture time and at every
+    call; a head wrapped in DistributedDataParallel, or a CPU tensor, is refused."""
+
+    def __init__(self, head, feats, world2pixel, origin, autocast_dtype=torch.bfloat16, occ_threshold=0.25, pair_capacity=None,
+                 warmup=2):
+        who = 'GraphedInference'
+        if isinstance(head, torch.nn.parallel.DistributedDataParallel):
+            raise RuntimeError('%s: a DistributedDataParallel head: inference needs no gradient exchange; pass the unwrapped '
+                               'module (head.module)' % who)
+        if head.training:
+            raise RuntimeError('%s: the head is in training mode; inference is captured in eval mode (head.eval())' % who)
+        head._check_infer()
+        self._need_gpu(feats, world2pixel, origin)
+        self.head, self.autocast_dtype, self.occ_threshold = head, autocast_dtype, float(occ_threshold)
+        self.pair_capacity = None if pair_capacity is None else int(pair_capacity)
+        self.inputs = tuple(t.detach().clone() for t in (feats, world2pixel, origin))
+        call = lambda out=None: head.infer(*self.inputs, occ_threshold=self.occ_threshold, pair_capacity=self.pair_capacity,
+                                           autocast_dtype=self.autocast_dtype, out=out)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):                 # (at least one: handles, plan and tables must exist before the capture)
+                outs = call()
+            self._clean_warmup = bool(torch.isfinite(outs.volume).all())
+            self._unchecked = 3
+            outs = None
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.outputs = call()
+
+    @staticmethod
+    def _need_gpu(feats, world2pixel, origin):
+        cpu = [k for k, t in (('feats', feats), ('world2pixel', world2pixel), ('origin', origin)) if not t.is_cuda]
+        if cpu:
+            raise RuntimeError('GraphedInference needs GPU tensors (HIP graphs); on the CPU: %s' % ', '.join(cpu))
+
+    @staticmethod
+    def _signature(feats, world2pixel, origin):
+        return (('feats', feats.shape, feats.dtype, None), ('world2pixel', world2pixel.shape, world2pixel.dtype, None),
+                ('origin', origin.shape, origin.dtype, None))
+
+    def __call__(self, feats, world2pixel, origin):
+        who = 'GraphedInference'
+        if self.head.training:
+            raise RuntimeError('%s: the head is in training mode; it was captured in eval mode (head.eval())' % who)
+        self._need_gpu(feats, world2pixel, origin)
+        check_step_inputs(who, self._signature(*self.inputs), self._signature(feats, world2pixel, origin))
+        for dst, src in zip(self.inputs, (feats, world2pixel, origin)):
+            if src is not dst:
+                dst.copy_(src, non_blocking=True)
+        self.graph.replay()
+        if self._unchecked:
+            # as the training graphs: the first replays are checked (one synchronisation each) for the runtime's memset-node problem
+            self._unchecked -= 1
+            if not bool(torch.isfinite(self.outputs.volume).all()) and self._clean_warmup:
+                raise RuntimeError(
+                    '%s: the volume of a replayed step is not finite although the eager warm-up calls were clean.  The '
+                    "package's import-time environment handling (vln-ver_amd/__init__.py) only takes effect if vln-ver_amd was "
+                    'imported BEFORE the first GPU call of the process; see GraphedTrainStep for the same check.' % who)
+        return self.outputs
+
+    def results(self, img_metas=None):
+        """The last replay's outputs as ``VoxelFormer.simple_test`` returns them: ONE device -> host copy of all tables."""
+        from .dense_heads.voxelformer_occupancy_head import inference_results
+        return inference_results(self.head, self.outputs, img_metas)

@@ -1482,6 +1482,32 @@ def occ_predict(logits, threshold=0.25):
     return pairs[:int(count.item())]
 
 
+def occ_predict_classes(logits, threshold=0.25):
+    """The class byte of every row under ``occ_predict``'s rule -- the same kernels, so the same decisions bit for bit --
+    WITHOUT the host read of the pair count: logits fp32|bf16 [..., C] -> uint8 [...], ``C`` = empty.  The compaction's
+    (row, class) pairs are scattered back into a dense map; the slots at and past the device-side count are steered to a
+    spare element by integer masking.  Launches only: capturable."""
+    logits = _gpu(logits, 'logits')
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        logits = logits.float()
+    lead, c = logits.shape[:-1], logits.shape[-1]
+    logits = logits.reshape(-1, c).contiguous()
+    n = logits.shape[0]
+    cls = torch.full((n + 1,), c, dtype=torch.uint8, device=logits.device)
+    if n == 0:
+        return cls[:0].view(lead)
+    dt = 1 if logits.dtype == torch.bfloat16 else 0
+    work = torch.empty(lib().ver_occ_predict_blocks(n), dtype=torch.int32, device=logits.device)
+    pairs = torch.empty(n, 2, dtype=torch.int64, device=logits.device)
+    count = torch.empty(1, dtype=torch.int64, device=logits.device)
+    _launch('ver_occ_predict', lambda: lib().ver_occ_predict(
+        _p(logits), dt, n, c, threshold, _p(work), _p(pairs), _p(count), _stream()))
+    live = (torch.arange(n, device=logits.device) < count).to(torch.int64)      # 1 for the pairs the kernel wrote
+    row = pairs[:, 0] * live + (1 - live) * n                                   # (an unwritten slot holds anything: times 0)
+    cls.scatter_(0, row, (pairs[:, 1] * live).to(torch.uint8))
+    return cls[:n].view(lead)
+
+
 def occ_confusion(logits, labels, thresholds=(0.25,), samples=1, hist=None):
     """Occupancy confusion matrix (ver_occ_confusion; the histogram of the reference's ``SSCMetrics.add_batch``):
     logits fp32|bf16 [samples * rows, C] (any leading shape), labels u8 with one entry per logit row in the same order
@@ -2117,6 +2143,140 @@ def occ_targets(pairs, offsets, voxel_num, zdim, classes, row_table=None, invali
         _p(pairs), code(pairs), _p(offsets), pairs.shape[0], _p(invalid), code(invalid), _p(invalid_offsets), n_invalid,
         _p(row_table), _p(labels), _p(count), _p(bad), voxel_num, zdim, classes, bs, _stream()))
     return labels, count, bad
+
+
+# ------------------------------------------------------------------------------------------
+# Occupancy pairs (ver_occ_pairs): byte labels of a batch -> per-sample sparse (voxel, class) pairs with offsets, the inverse
+# of occ_targets, in fixed shapes and without a host read.
+def occ_pairs_block_size():
+    """Voxels of one sample a workgroup of ``ver_occ_pairs`` covers: its scratch holds one int32 per such block."""
+    return int(lib().ver_occ_pairs_block_size())
+
+
+def _occ_pairs_sizes(who, bs, voxel_num, zdim, classes, capacity, flat, int32_pairs):
+    bs, voxel_num, zdim, classes = int(bs), int(voxel_num), int(zdim), int(classes)
+    if bs < 0 or voxel_num < 0 or zdim < 1 or not 1 <= classes < 255 or voxel_num % zdim:
+        raise ValueError('%s: bs=%d voxel_num=%d zdim=%d classes=%d (1 <= classes < 255, voxel_num %% zdim == 0)'
+                         % (who, bs, voxel_num, zdim, classes))
+    if bs * voxel_num >= 2 ** 31:
+        raise ValueError('%s: %d x %d labels do not fit 2^31%s' % (who, bs, voxel_num, ' (nor do flattened-batch indices fit '
+                                                                    'int32 pairs)' if flat and int32_pairs else ''))
+    capacity = bs * voxel_num if capacity is None else int(capacity)
+    if not 0 <= capacity < 2 ** 31:
+        raise ValueError('%s: capacity=%d' % (who, capacity))
+    return bs, voxel_num, zdim, classes, capacity
+
+
+def occ_pairs_host(labels, bs, voxel_num, zdim, classes, row_table=None, capacity=None, flat=False, dtype=torch.int32):
+    """The contract of ``ver_occ_pairs`` (include/ver_ops.h) in numpy, written from its semantics: the model the tests hold the
+    kernel to, and the CPU route.  labels uint8 [bs * voxel_num] in the reference's (Z, X, Y) voxel order, or -- with
+    ``row_table`` int [voxel_num / zdim, 3] -- in the group-major row order ``occ_targets_host`` writes.
+    -> (pairs [capacity, 2] of ``dtype`` (int32 | int64), offsets int32 [bs + 1], count int32 [bs + 2]).
+    A byte < ``classes`` is an occupied voxel; ``classes`` and anything above produce nothing.  pairs: (voxel index within
+    the sample -- plus ``b * voxel_num`` with ``flat`` --, class), ascending within a sample, sample after sample; only the
+    first ``min(total, capacity)`` are written (zeros behind them here).  offsets: exclusive prefix sums of the per-sample
+    counts, each clamped to ``capacity``.  count: the true count of every sample, the true total, then 1 if the total
+    exceeded ``capacity``.  ``capacity=None``: ``bs * voxel_num``, which no batch overflows."""
+    import numpy as np
+    np_dtype = {torch.int32: np.int32, torch.int64: np.int64}.get(dtype, dtype)
+    if np_dtype not in (np.int32, np.int64):
+        raise TypeError('occ_pairs_host: pairs are int32 or int64, got %s' % (dtype,))
+    bs, voxel_num, zdim, classes, capacity = _occ_pairs_sizes('occ_pairs_host', bs, voxel_num, zdim, classes, capacity, flat,
+                                                              np_dtype == np.int32)
+    lab = np.asarray(labels).reshape(-1)
+    if lab.dtype != np.uint8 or lab.size != bs * voxel_num:
+        raise ValueError('occ_pairs_host: labels must be %d uint8, got %d %s' % (bs * voxel_num, lab.size, lab.dtype))
+    rows = voxel_num // zdim
+    if row_table is None:
+        vol = lab.reshape(bs, voxel_num)
+    else:
+        table = np.asarray(row_table).astype(np.int64)
+        if table.shape != (rows, 3):
+            raise ValueError('occ_pairs_host: row_table must be [%d, 3], got %s' % (rows, table.shape))
+        z, q = np.divmod(np.arange(voxel_num, dtype=np.int64), rows)
+        # [bs, voxel_num]: byte of (sample, voxel), occ_targets_host's formula
+        where = ((bs * table[q, 0])[None, :] + np.arange(bs, dtype=np.int64)[:, None] * table[q, 1][None, :]
+                 + table[q, 2][None, :]) * zdim + z[None, :]
+        inside = (where >= 0) & (where < bs * voxel_num)
+        vol = np.where(inside, lab[np.where(inside, where, 0)], classes).astype(np.uint8) if lab.size else lab.reshape(bs, voxel_num)
+    count = np.zeros(bs + 2, dtype=np.int32)
+    found = []
+    for b in range(bs):
+        v = np.flatnonzero(vol[b] < classes)
+        count[b] = v.size
+        found.append(np.stack([v + (b * voxel_num if flat else 0), vol[b][v].astype(np.int64)], axis=1))
+    total = int(count[:bs].sum())
+    count[bs], count[bs + 1] = total, int(total > capacity)
+    offsets = np.minimum(np.concatenate([[0], np.cumsum(count[:bs], dtype=np.int64)]), capacity).astype(np.int32)
+    pairs = np.zeros((capacity, 2), dtype=np_dtype)
+    if found:
+        kept = np.concatenate(found)[:capacity]
+        pairs[:kept.shape[0]] = kept
+    return pairs, offsets, count
+
+
+class OccPairsGts(PackedOccGts):
+    """``(pairs, offsets)`` of ``occ_pairs`` (per-sample indices, ``flat=False``) as the ``PackedOccGts`` that ``occ_targets``
+    and ``head.occupancy_targets_device`` take -- the round trip: ``occ_targets(g.pairs, g.offsets, ...)`` visits
+    ``[offsets[b], offsets[b + 1])`` of every sample and nothing behind ``offsets[bs]``.  A view: no copy, no host read."""
+
+    def __init__(self, pairs, offsets):
+        if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.dtype not in (torch.int32, torch.int64) or offsets.dim() != 1 \
+                or offsets.dtype != torch.int32 or offsets.numel() < 1 or offsets.device != pairs.device:
+            raise TypeError('OccPairsGts: pairs int32 | int64 [capacity, 2] and offsets int32 [bs + 1] on one device')
+        self.buffer, self.bs, self.n_total, self.n_invalid, self.has_invalid = pairs, offsets.numel() - 1, pairs.shape[0], 0, False
+        self._slot = self._generation = None
+        self.pairs, self.offsets, self.invalid, self.invalid_offsets = pairs, offsets, None, None
+
+    def to(self, device):
+        return OccPairsGts(self.pairs.to(device), self.offsets.to(device))
+
+
+def occ_pairs(labels, bs, voxel_num, zdim, classes, row_table=None, capacity=None, flat=False, dtype=torch.int32, out=None):
+    """Per-sample sparse pairs of a batch of byte labels (ver_occ_pairs; semantics: ``occ_pairs_host``): labels uint8
+    [bs * voxel_num] on the GPU (any shape with that many elements), in the reference's voxel order or -- with ``row_table``
+    int32 [voxel_num / zdim, 3] (``occ_proj_lattice.row_table``) -- in the GEMMs' row order, e.g. as ``occ_mlp_classes`` leaves
+    them.  -> (pairs ``dtype`` [capacity, 2], offsets int32 [bs + 1], count int32 [bs + 2]); ``capacity=None``:
+    ``bs * voxel_num``.  ``flat``: voxel indices over the flattened batch, what ``occupancy_pairs_from_classes`` returns.
+    ``out``: ``(pairs, offsets, count)`` of an earlier call with the same sizes to write into -- offsets, count and the
+    kernel's scratch are one allocation, so such a call allocates nothing.  Three launches, no host synchronisation,
+    capturable; sample b's pairs are ``pairs[offsets[b]:offsets[b + 1]]`` once the host knows the offsets."""
+    what = 'occ_pairs'
+    labels = _gpu(labels, 'labels', torch.uint8).reshape(-1)
+    dev = labels.device
+    if dtype not in (torch.int32, torch.int64):
+        raise TypeError('%s: pairs are int32 or int64, got %s' % (what, dtype))
+    bs, voxel_num, zdim, classes, capacity = _occ_pairs_sizes(what, bs, voxel_num, zdim, classes, capacity, flat,
+                                                              dtype == torch.int32)
+    if labels.numel() != bs * voxel_num:
+        raise ValueError('%s: %d labels for %d x %d voxels' % (what, labels.numel(), bs, voxel_num))
+    if row_table is not None:
+        row_table = _gpu(row_table, 'row_table', torch.int32)
+        if tuple(row_table.shape) != (voxel_num // zdim, 3) or row_table.device != dev:
+            raise ValueError('%s: row_table must be int32 %s on %s' % (what, (voxel_num // zdim, 3), dev))
+    nb = int(lib().ver_occ_pairs_blocks(bs, voxel_num))
+    head = 2 * bs + 3
+    if out is None:
+        pairs = torch.empty(capacity, 2, dtype=dtype, device=dev)
+        # (zeros: a call with bs == 0 or voxel_num == 0 launches nothing and still returns offsets and counts)
+        meta = torch.zeros(head + nb, dtype=torch.int32, device=dev) if nb == 0 else torch.empty(head + nb, dtype=torch.int32, device=dev)
+        offsets, count, work = meta[:bs + 1], meta[bs + 1:head], meta[head:]
+    else:
+        pairs, offsets, count = out
+        if (pairs.dtype != dtype or tuple(pairs.shape) != (capacity, 2) or not pairs.is_contiguous() or pairs.device != dev):
+            raise ValueError('%s: out pairs must be contiguous %s %s on %s' % (what, dtype, (capacity, 2), dev))
+        for t, name, n in ((offsets, 'out offsets', bs + 1), (count, 'out count', bs + 2)):
+            if t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != dev:
+                raise ValueError('%s: %s must be contiguous int32 [%d] on %s' % (what, name, n, dev))
+        room = offsets.untyped_storage().nbytes() // 4 - offsets.storage_offset()
+        if count.data_ptr() == offsets.data_ptr() + 4 * (bs + 1) and room >= head + nb:
+            work = offsets.as_strided((nb,), (1,), offsets.storage_offset() + head)       # the earlier call's scratch
+        else:
+            work = torch.empty(nb, dtype=torch.int32, device=dev)
+    _launch('ver_occ_pairs', lambda: lib().ver_occ_pairs(
+        _p(labels), _p(row_table), _p(pairs), 1 if dtype == torch.int64 else 0, _p(offsets), _p(count), _p(work), capacity,
+        voxel_num, zdim, classes, bs, 1 if flat else 0, _stream()))
+    return pairs, offsets, count
 
 
 # ------------------------------------------------------------------------------------------
