@@ -1049,6 +1049,47 @@ int  ver_occ_pairs(const uint8_t* labels, const int32_t* row_table, void* pairs,
                    int32_t* count, int32_t* block_work, long capacity, long voxel_num, int zdim, int classes, int bs,
                    int flags, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * A batch out of a device-resident viewpoint store, by index (additive to ABI 31; csrc/ver_fetch.hip).  The reference keeps
+ * the feature maps it has read in a host dict (detectors/voxelformer.py:317-325) and re-reads the occupancy annotation on
+ * every step; here the whole split lives in device memory and a step's batch is gathered straight into the static buffers
+ * of a captured step, the only host -> device traffic being the index vector.
+ *   index        i32 [bs], device memory: read by the kernels, never by the host.  A value outside [0, V) makes an EMPTY
+ *                sample: zero feature and camera rows, count 0, no pairs; nothing is read outside the store.
+ * Four groups, each may be absent (all of its pointers NULL):
+ *  features      feat_store f32 | bf16 [V, ncam, row] -> feat_out [ncam, bs, row], same dtype (feat_dtype = VER_F32 |
+ *                VER_BF16): a pure copy, bit for bit, with 64-bit element offsets and the widest access (16, 8, 4 or 2 bytes)
+ *                that divides the row bytes and both base addresses; any row >= 1 works (row == 0 copies nothing).
+ *  cameras       w2p_store f32 [V, ncam, 4, 4] -> w2p_out [bs, ncam, 4, 4];  origin_store f32 [V, 3] -> origin_out [bs, 3]
+ *  boxes         box_store f32 [V, store_cap, box_dim], label_store i64 [V, store_cap], count_store i32 [V] ->
+ *                box_out f32 [bs, out_cap, box_dim], label_out i64 [bs, out_cap], count_out i32 [bs] (a PaddedGts): the first
+ *                min(count, out_cap) rows of a sample are copied and count_out[b] is that minimum; columns at or past it are
+ *                left as they were.  box_store / label_store may be NULL when store_cap == 0, box_out / label_out when
+ *                out_cap == 0.  (A stored count is read as clamped to [0, store_cap].)
+ *  pairs         CSR: pair_store i32 [pair_total][2], pair_offsets i64 [V + 1] -> offsets_out i32 [bs + 1], pairs_out i32
+ *                [pair_capacity][2] (the views of a PackedOccGts): offsets are the exclusive prefix sums of the fetched
+ *                lengths, each clamped to pair_capacity; the pairs of sample b are copied in order into
+ *                [offsets[b], offsets[b+1]); pairs past the capacity are dropped; what lies behind the live pairs is left as
+ *                it was.  pair_store may be NULL when pair_total == 0, pairs_out when pair_capacity == 0.  (CSR bounds are
+ *                read as clamped to [0, pair_total] and never descending.)
+ *   status       i32 [4], written in full by every call (never ORed, no zeroing needed): [0] samples whose index was outside
+ *                [0, V); [1] samples whose box count exceeded out_cap; [2] 1 if the pairs overflowed pair_capacity, else 0;
+ *                [3] the true pair total, saturated at 2^31 - 1.  Words of an absent group are 0.
+ * At most four launches (a one-workgroup scan of the bs lengths, then the copies of the present groups), plain vector
+ * stores, no memset node, no allocation, no host read: the call can be captured, and a replay after the index buffer changed
+ * fetches the new batch.  ver_fetch_pair_tile(): the output pair slots one workgroup of the pair copy covers.
+ * bs == 0: VER_OK, nothing is launched and no pointer is looked at.  Negative sizes, an unknown dtype, a null index or
+ * status, a null or misaligned pointer of a present group (features: one element; pairs and labels: 8 bytes; else 4):
+ * VER_EINVAL.  bs >= 65 536, ncam >= 65 536 or pair_capacity >= 2^31: VER_EUNSUPPORTED.
+ */
+long ver_fetch_pair_tile(void);
+int  ver_fetch_batch(const int32_t* index, int bs, long V, int ncam, const void* feat_store, void* feat_out, int feat_dtype,
+                     long row, const float* w2p_store, const float* origin_store, float* w2p_out, float* origin_out,
+                     const float* box_store, const int64_t* label_store, const int32_t* count_store, float* box_out,
+                     int64_t* label_out, int32_t* count_out, int store_cap, int out_cap, int box_dim,
+                     const int32_t* pair_store, const int64_t* pair_offsets, long pair_total, int32_t* offsets_out,
+                     int32_t* pairs_out, long pair_capacity, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 LIB = os.path.join(PKG, 'libver_hip.so')
-SOURCES = ['ver_abi.hip', 'ver_msda.hip', 'ver_sca.hip', 'ver_lattice.hip', 'ver_mlp.hip', 'ver_loss.hip', 'ver_occ_mlp.hip', 'ver_layout.hip', 'ver_addln.hip', 'ver_post.hip', 'ver_wgrad.hip', 'ver_gemm.hip', 'ver_optim.hip', 'ver_assign.hip', 'ver_boxiou.hip', 'ver_setloss.hip', 'ver_decode.hip', 'ver_targets.hip', 'ver_pairs.hip', 'ver_dattn3d.hip', 'ver_mha.hip']
+SOURCES = ['ver_abi.hip', 'ver_msda.hip', 'ver_sca.hip', 'ver_lattice.hip', 'ver_mlp.hip', 'ver_loss.hip', 'ver_occ_mlp.hip', 'ver_layout.hip', 'ver_addln.hip', 'ver_post.hip', 'ver_wgrad.hip', 'ver_gemm.hip', 'ver_optim.hip', 'ver_assign.hip', 'ver_boxiou.hip', 'ver_setloss.hip', 'ver_decode.hip', 'ver_targets.hip', 'ver_pairs.hip', 'ver_fetch.hip', 'ver_dattn3d.hip', 'ver_mha.hip']
 HEADERS = ['ver_common.h', 'ver_classify.h', 'ver_gemm_tile.h', os.path.join('..', '..', 'include', 'ver_ops.h')]
 FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-shared', '-munsafe-fp-atomics',
          '-Wall', '-Wno-unused-function']

@@ -272,6 +272,30 @@ def check_step_inputs(who, captured, offered):
             raise ValueError('%s: %s is %s %s, captured with %s %s' % (who, name, got, got_dtype, shape, dtype))
 
 
+def _fetch_into(who, step, store, index, gts, occ):
+    """``store.fetch`` (``resident.ResidentStore``) straight into a captured step's static buffers: eager launches on the
+    current stream, in front of the replay.  The store's camera count, row size and dtype are held against the captured
+    feature buffer first, on host data alone and before any launch.  -> the status tensor (``store.check`` reads it)."""
+    from .resident import ResidentBatch
+    feats = step.inputs[0]
+    if store.device != feats.device:
+        raise RuntimeError('%s: the store lives on %s, the captured buffers on %s' % (who, store.device, feats.device))
+    row = 1
+    for s in feats.shape[2:]:
+        row *= int(s)
+    check_step_inputs(who, (('the store\'s viewpoint features [Ncam, row]', (feats.shape[0], row), feats.dtype, None),),
+                      (('', (store.num_cams, store.row), store.feat_dtype, None),))
+    batch = getattr(step, '_resident', None)
+    if batch is None:
+        dev = feats.device
+        batch = step._resident = ResidentBatch(*step.inputs, gts, occ, torch.zeros(4, dtype=torch.int32, device=dev),
+                                               torch.zeros(feats.shape[1], dtype=torch.int32, device=dev))
+    n = index.numel() if torch.is_tensor(index) else len(index)
+    if n != feats.shape[1]:
+        raise ValueError('%s: %d indices for a captured batch of %d' % (who, n, feats.shape[1]))
+    return store.fetch(index, out=batch).status
+
+
 class GraphedTrainStep:
     """One training step of the WHOLE head -- encoder, detection decoder, cls / reg branches, coarse-to-fine occupancy,
     occupancy targets from the sparse pairs, the set loss of every decoder layer, the occupancy focal loss, backward, gradient
@@ -503,6 +527,14 @@ class GraphedTrainStep:
                     'vln-ver_amd sets it, but only takes effect if HIP was not initialised earlier.' % who)
         return self.losses
 
+    def fetch(self, store, index):
+        """The ground truth and inputs of the next step out of a ``resident.ResidentStore``, written by the device into
+        ``self.inputs``, ``self.gts`` and the ``offsets`` / ``pairs`` views of ``self.occ`` (at ``self.pair_capacity``):
+        ``step.fetch(store, idx); step(*step.inputs, step.gts, step.occ)`` is a step whose only host -> device traffic is
+        the ``4 * bs`` bytes of a host ``idx`` (none for a device tensor).  A store with another camera count, row size or
+        feature dtype is refused before any launch.  -> the status tensor of the fetch (``store.check(status)``)."""
+        return _fetch_into('GraphedTrainStep.fetch', self, store, index, self.gts, self.occ)
+
     def flags(self):
         """What the replayed steps could only report on the device, read now (ONE synchronisation): ``assignment`` -- the
         sticky ``AssignmentFlag`` (a cost matrix ``lsa_solve`` could not assign); ``label_range`` -- the sticky
@@ -595,6 +627,12 @@ class GraphedInference:
                     "package's import-time environment handling (vln-ver_amd/__init__.py) only takes effect if vln-ver_amd was "
                     'imported BEFORE the first GPU call of the process; see GraphedTrainStep for the same check.' % who)
         return self.outputs
+
+    def fetch(self, store, index):
+        """The inputs of the next call out of a ``resident.ResidentStore`` (features and cameras; no ground truth), written
+        by the device into ``self.inputs``: ``step.fetch(store, idx); step(*step.inputs)``.  A store with another camera
+        count, row size or feature dtype is refused before any launch.  -> the status tensor (``store.check(status)``)."""
+        return _fetch_into('GraphedInference.fetch', self, store, index, None, None)
 
     def results(self, img_metas=None):
         """The last replay's outputs as ``VoxelFormer.simple_test`` returns them: ONE device -> host copy of all tables."""

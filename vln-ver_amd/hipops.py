@@ -2280,6 +2280,182 @@ def occ_pairs(labels, bs, voxel_num, zdim, classes, row_table=None, capacity=Non
 
 
 # ------------------------------------------------------------------------------------------
+# A batch out of a device-resident viewpoint store (ver_fetch_batch): features, cameras, padded box tables and sparse pairs
+# of the viewpoints an index vector names, written into buffers of fixed shapes without a host read (resident.ResidentStore).
+def fetch_pair_tile():
+    """Output pair slots one workgroup of ``ver_fetch_batch``'s pair copy covers."""
+    return int(lib().ver_fetch_pair_tile())
+
+
+def fetch_batch_host(index, V=None, feats=None, world2pixel=None, origin=None, boxes=None, labels=None, counts=None,
+                     pairs=None, pair_offsets=None, out_cap=None, pair_capacity=None, out=None):
+    """The contract of ``ver_fetch_batch`` (include/ver_ops.h) in numpy, written from its semantics: the model the tests hold
+    the kernels to, and the CPU route of ``ResidentStore.fetch``.  ``index`` int [bs]; the store's tables as arrays, a group
+    being absent when its tables are None: ``feats [V, Ncam, row]`` (any dtype: a pure copy); ``world2pixel [V, Ncam, 4, 4]``
+    with ``origin [V, 3]``; ``boxes [V, store_cap, box_dim]``, ``labels [V, store_cap]``, ``counts [V]`` with ``out_cap``;
+    ``pairs [total, 2]`` with ``pair_offsets [V + 1]`` (CSR) and ``pair_capacity``.  ``out``: a dict of earlier outputs
+    (``boxes``, ``labels``, ``pairs``) whose contents past the counts / behind the live pairs are KEPT; zeros without it.
+    -> dict of the present groups' outputs -- ``feats [Ncam, bs, row]``, ``world2pixel [bs, Ncam, 4, 4]``, ``origin [bs, 3]``,
+    ``boxes f32 [bs, out_cap, box_dim]``, ``labels int64 [bs, out_cap]``, ``counts int32 [bs]``, ``offsets int32 [bs + 1]``,
+    ``pairs int32 [pair_capacity, 2]`` -- and ``status`` int32 [4].
+    A sample whose index is outside [0, V) is empty: zero features and cameras, count 0, no pairs.  A sample's first
+    min(count, out_cap) box rows are copied and that minimum is its count.  offsets: exclusive prefix sums of the fetched
+    pair lengths, each clamped to the capacity; pairs past the capacity are dropped.  status: samples with an index outside
+    the store; samples whose count exceeded ``out_cap``; 1 if the pairs overflowed; the true pair total, saturated at
+    2^31 - 1."""
+    import numpy as np
+    idx = np.asarray(index).reshape(-1).astype(np.int64)
+    bs = idx.size
+    for t in (feats, world2pixel, counts):
+        if V is None and t is not None:
+            V = t.shape[0]
+    if V is None:
+        V = (np.asarray(pair_offsets).size - 1) if pair_offsets is not None else 0
+    V = int(V)
+    ok = (idx >= 0) & (idx < V)
+    safe = np.where(ok, idx, 0)
+    out = dict(out or {})
+    res = {}
+    status = np.zeros(4, dtype=np.int32)
+    status[0] = int((~ok).sum())
+    if feats is not None:
+        feats = np.asarray(feats)
+        if feats.ndim != 3 or feats.shape[0] != V:
+            raise ValueError('fetch_batch_host: feats must be [%d, Ncam, row], got %s' % (V, feats.shape))
+        got = np.zeros((feats.shape[1], bs, feats.shape[2]), dtype=feats.dtype)
+        if V and bs:
+            got[:, ok] = feats[safe[ok]].transpose(1, 0, 2)
+        res['feats'] = got
+    if (world2pixel is None) != (origin is None):
+        raise ValueError('fetch_batch_host: world2pixel and origin come together')
+    if world2pixel is not None:
+        w2p, org = np.asarray(world2pixel, dtype=np.float32), np.asarray(origin, dtype=np.float32)
+        if w2p.ndim != 4 or w2p.shape[0] != V or w2p.shape[2:] != (4, 4) or org.shape != (V, 3):
+            raise ValueError('fetch_batch_host: world2pixel [%d, Ncam, 4, 4] and origin [%d, 3], got %s and %s' % (V, V, w2p.shape, org.shape))
+        res['world2pixel'] = np.zeros((bs,) + w2p.shape[1:], dtype=np.float32)
+        res['origin'] = np.zeros((bs, 3), dtype=np.float32)
+        if V and bs:
+            res['world2pixel'][ok] = w2p[safe[ok]]
+            res['origin'][ok] = org[safe[ok]]
+    if counts is not None:
+        boxes, labels, counts = np.asarray(boxes, dtype=np.float32), np.asarray(labels).astype(np.int64), np.asarray(counts).astype(np.int64)
+        if boxes.ndim != 3 or boxes.shape[0] != V or labels.shape != boxes.shape[:2] or counts.shape != (V,) or out_cap is None:
+            raise ValueError('fetch_batch_host: boxes [%d, cap, dim], labels [%d, cap], counts [%d] and out_cap' % (V, V, V))
+        store_cap, dim, out_cap = boxes.shape[1], boxes.shape[2], int(out_cap)
+        got_b = np.array(out['boxes'], dtype=np.float32) if 'boxes' in out else np.zeros((bs, out_cap, dim), dtype=np.float32)
+        got_l = np.array(out['labels'], dtype=np.int64) if 'labels' in out else np.zeros((bs, out_cap), dtype=np.int64)
+        got_c = np.zeros(bs, dtype=np.int32)
+        for b in range(bs):
+            if ok[b]:
+                c = int(counts[idx[b]])
+                status[1] += int(c > out_cap)
+                n = min(max(c, 0), store_cap, out_cap)
+                got_b[b, :n] = boxes[idx[b], :n]
+                got_l[b, :n] = labels[idx[b], :n]
+                got_c[b] = n
+        res.update(boxes=got_b, labels=got_l, counts=got_c)
+    if pair_offsets is not None:
+        po = np.asarray(pair_offsets).astype(np.int64)
+        pairs = np.asarray(pairs if pairs is not None else np.zeros((0, 2)), dtype=np.int32).reshape(-1, 2)
+        if po.shape != (V + 1,) or pair_capacity is None:
+            raise ValueError('fetch_batch_host: pair_offsets must be [%d] and pair_capacity given' % (V + 1))
+        cap = int(pair_capacity)
+        lo = np.clip(po[:-1], 0, pairs.shape[0])
+        hi = np.clip(np.maximum(po[1:], lo), 0, pairs.shape[0])
+        lens = np.where(ok, (hi - lo)[safe] if V else 0, 0).astype(np.int64)
+        starts = np.concatenate([[0], np.cumsum(lens)])
+        total = int(starts[-1])
+        got_p = np.array(out['pairs'], dtype=np.int32) if 'pairs' in out else np.zeros((cap, 2), dtype=np.int32)
+        for b in range(bs):
+            n = max(0, min(int(starts[b + 1]), cap) - int(starts[b]))
+            if n:
+                got_p[starts[b]:starts[b] + n] = pairs[lo[idx[b]]:lo[idx[b]] + n]
+        res.update(offsets=np.minimum(starts, cap).astype(np.int32), pairs=got_p)
+        status[2], status[3] = int(total > cap), min(total, 2 ** 31 - 1)
+    res['status'] = status
+    return res
+
+
+def fetch_batch(index, V, feats=None, cameras=None, boxes=None, pairs=None, status=None):
+    """``ver_fetch_batch`` (semantics: ``fetch_batch_host``): ``index`` int32 [bs] ON THE GPU, read by the kernels alone; ``V``
+    viewpoints in the store.  Each group is a tuple of GPU tensors or None (absent):
+    ``feats = (store [V, Ncam, row] f32 | bf16, out [Ncam, bs, ...] of row elements per (camera, sample))``;
+    ``cameras = (w2p_store [V, Ncam, 4, 4], origin_store [V, 3], w2p_out [bs, Ncam, 4, 4], origin_out [bs, 3])`` f32;
+    ``boxes = (box_store f32 [V, store_cap, dim], label_store int64 [V, store_cap], count_store int32 [V], box_out f32
+    [bs, out_cap, dim], label_out int64 [bs, out_cap], count_out int32 [bs])``;
+    ``pairs = (pair_store int32 [total, 2], pair_offsets int64 [V + 1], offsets_out int32 [bs + 1], pairs_out int32
+    [pair_capacity, 2])``.  ``status``: int32 [4] to write (allocated when None) -> status.  Every shape is checked here, on
+    the host; at most four launches, no synchronisation, capturable."""
+    what = 'fetch_batch'
+    index = _gpu(index, 'index', torch.int32)
+    dev = index.device
+    if index.dim() != 1:
+        raise ValueError('%s: index must be int32 [bs], got %s' % (what, tuple(index.shape)))
+    bs, V = index.numel(), int(V)
+    if V < 0:
+        raise ValueError('%s: V=%d' % (what, V))
+
+    def need(t, name, dtype, shape):
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev or t.dtype != dtype or tuple(t.shape) != tuple(shape) \
+                or not t.is_contiguous():
+            raise ValueError('%s: %s must be contiguous %s %s on %s, got %s' % (
+                what, name, dtype, tuple(shape), dev,
+                '%s %s on %s' % (t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__))
+        return t
+
+    ncam = 0
+    f_store = f_out = w_store = o_store = w_out = o_out = None
+    b_store = l_store = c_store = b_out = l_out = c_out = p_store = p_off = off_out = p_out = None
+    f_dtype, row, store_cap, out_cap, dim, total, cap = 0, 0, 0, 0, 0, 0, 0
+    if feats is not None:
+        f_store, f_out = feats
+        if f_store.dim() != 3 or f_store.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError('%s: the feature store is f32 or bf16 [V, Ncam, row], got %s %s' % (what, f_store.dtype, tuple(f_store.shape)))
+        ncam, row = int(f_store.shape[1]), int(f_store.shape[2])
+        need(f_store, 'feat_store', f_store.dtype, (V, ncam, row))
+        if f_out.dim() < 2 or f_out.numel() != ncam * bs * row:
+            raise ValueError('%s: feat_out %s does not hold [%d, %d] rows of %d' % (what, tuple(f_out.shape), ncam, bs, row))
+        need(f_out, 'feat_out', f_store.dtype, (ncam, bs) + tuple(f_out.shape[2:]))
+        f_dtype = 1 if f_store.dtype == torch.bfloat16 else 0
+    if cameras is not None:
+        w_store, o_store, w_out, o_out = cameras
+        if w_store.dim() != 4 or (feats is not None and w_store.shape[1] != ncam):
+            raise ValueError('%s: w2p_store %s beside %d cameras of features' % (what, tuple(w_store.shape), ncam))
+        ncam = int(w_store.shape[1])
+        need(w_store, 'w2p_store', torch.float32, (V, ncam, 4, 4))
+        need(o_store, 'origin_store', torch.float32, (V, 3))
+        need(w_out, 'w2p_out', torch.float32, (bs, ncam, 4, 4))
+        need(o_out, 'origin_out', torch.float32, (bs, 3))
+    if boxes is not None:
+        b_store, l_store, c_store, b_out, l_out, c_out = boxes
+        if b_store.dim() != 3 or b_out.dim() != 3:
+            raise ValueError('%s: box_store [V, store_cap, dim] and box_out [bs, out_cap, dim]' % what)
+        store_cap, dim, out_cap = int(b_store.shape[1]), int(b_store.shape[2]), int(b_out.shape[1])
+        need(b_store, 'box_store', torch.float32, (V, store_cap, dim))
+        need(l_store, 'label_store', torch.int64, (V, store_cap))
+        need(c_store, 'count_store', torch.int32, (V,))
+        need(b_out, 'box_out', torch.float32, (bs, out_cap, dim))
+        need(l_out, 'label_out', torch.int64, (bs, out_cap))
+        need(c_out, 'count_out', torch.int32, (bs,))
+    if pairs is not None:
+        p_store, p_off, off_out, p_out = pairs
+        total, cap = int(p_store.shape[0]), int(p_out.shape[0])
+        need(p_store, 'pair_store', torch.int32, (total, 2))
+        need(p_off, 'pair_offsets', torch.int64, (V + 1,))
+        need(off_out, 'offsets_out', torch.int32, (bs + 1,))
+        need(p_out, 'pairs_out', torch.int32, (cap, 2))
+    status = torch.empty(4, dtype=torch.int32, device=dev) if status is None else need(status, 'status', torch.int32, (4,))
+    if bs == 0:
+        return status.zero_()
+    # (an empty tensor's address is 0 = NULL, which the C side takes where a table has no rows)
+    _launch('ver_fetch_batch', lambda: lib().ver_fetch_batch(
+        _p(index), bs, V, ncam, _p(f_store), _p(f_out), f_dtype, row, _p(w_store), _p(o_store), _p(w_out), _p(o_out),
+        _p(b_store), _p(l_store), _p(c_store), _p(b_out), _p(l_out), _p(c_out), store_cap, out_cap, dim,
+        _p(p_store), _p(p_off), total, _p(off_out), _p(p_out), cap, _p(status), _stream()))
+    return status
+
+
+# ------------------------------------------------------------------------------------------
 def wgrad_tn_supported(a, g):
     """Shapes / strides ``wgrad_tn`` takes: bf16 GPU matrices, unit column stride, 16-byte aligned rows."""
     return (a.is_cuda and g.is_cuda and a.dtype == torch.bfloat16 and g.dtype == torch.bfloat16 and a.dim() == 2
